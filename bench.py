@@ -9,17 +9,30 @@ magnitude, global-max dB normalisation -- i.e. BASELINE.json config 4
 For N > 1 GPUs each rank owns its own 4096-frame shard (weak scaling); the
 STFT halo, global max and range_speed gather run as RCCL collectives.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--fp16]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--fp16] [--dump-outputs DIR] [--full]
 
 --gpus N > 1 without a torchrun environment starts N ranks itself (a child
 torch.distributed.run, before any GPU call) and exits with its status; under
 torchrun the world size must equal --gpus.
 
-Rank 0 prints one JSON line (contract in the task statement).  After every
-timed region it checks the launches' sticky error word (fmcw_synchronize) and,
-in the oracle leg at the end (CPU baseline), compares every timed frame's
-outputs with the float64 C oracle (oracle/fmcw_oracle.c): the "checked" key.
-A failed check still prints the line, then exits non-zero.
+A plain run does what the headline figure needs and no more: set-up, W warm-up
+steps, K timed steps, the sticky error word of the launches (fmcw_synchronize)
+after each, and one JSON line from rank 0 (`value`, `ms_per_step`, and the
+k_rdx roofline from the HIP-event pair the timed steps carry anyway).
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed
+step left in the caller's buffers as DIR/<name>.npy (float32; dump_outputs()
+below: whole arrays where they are small, a fixed seeded sample of the RD map
+and of the STFT dB map, under 64 MB in all).  The inputs are seeded by global
+frame index, so two runs with the same arguments dump comparable arrays.
+
+--full adds every other measurement and check, each in a run of its own after
+the timed steps: the per-stage breakdown, the in-run HBM copy ceiling, the
+fp16-storage, config-2 and host-pointer lines, the input fan-out (N > 1), the
+CPU baseline and, in the oracle leg at the end, the comparison of every timed
+frame's outputs with the float64 C oracle (oracle/fmcw_oracle.c): the
+"checked" key.  A failed check still prints the line, then exits non-zero.
+The --no-* and --cpu-seconds options trim a --full run.
 """
 from __future__ import annotations
 
@@ -49,6 +62,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--frames", type=int, default=4096, help="frames per GPU per step")
     ap.add_argument("--fp16", action="store_true", help="config-4 fp16 storage variant")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the stage breakdown, the copy ceiling, the fp16 / config-2 / "
+                         "host-path lines, the input fan-out, the CPU baseline and the full-size oracle check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, < 64 MB in all)")
     ap.add_argument("--chunk", type=int, default=0, help="frames per range/Doppler chunk (0 = library default)")
     ap.add_argument("--pipeline", choices=["auto", "streams", "onepass", "xcd"], default="auto",
                     help="range/Doppler schedule (include/fmcw.h fmcw_set_pipeline)")
@@ -304,9 +322,13 @@ def main():
     stages = eng.timing_read() if level else {}
     eng.timing(0)
     sticky_check(eng, "timed steps")          # a timed-out k_rdx hand-off invalidates the run
+    dumped = None
+    if args.dump_outputs and rank == 0:       # before any later leg runs the step again
+        dumped = dump_outputs(args.dump_outputs, outs, d_rd, d_P, nseg)
+    full = args.full
     # the stage breakdown (every launch between event pairs) from a few steps after the timed ones
     breakdown = {}
-    if level:
+    if level and full:
         eng.timing(2)
         eng.timing_reset()
         nb_steps = 5
@@ -330,7 +352,7 @@ def main():
     # cube into an RD-sized buffer (8.6 + 8.6 GB, DESIGN 4.0.1 part A's shape)
     sclk_mhz, _ = eng.rdx_clock()
     copy = None
-    if not args.no_copy_ceiling:
+    if full and not args.no_copy_ceiling:
         copy = copy_ceiling(eng, d_iq, dev, stream, 5,
                             "16-byte nontemporal copy of the input cube into an RD-sized buffer (k_rdx's in + RD "
                             "bytes), one thread per 16 bytes, HIP events, same process")
@@ -400,15 +422,15 @@ def main():
 
     # ---- input fan-out over xGMI from rank 0 (reported separately, not in value) -----
     fanout = None
-    if world > 1 and not args.no_fanout:
+    if full and world > 1 and not args.no_fanout:
         fanout = input_fanout(dist, world, rank, 256, (C, S, 2), tdt, dev, barrier,
                               lambda: torch.cuda.synchronize(dev))
 
     extra, legs = {}, []
-    if rank == 0 and not args.no_check:
+    if full and rank == 0 and not args.no_check:
         legs.append(dict(name="config4_f32" if not args.fp16 else "config4_fp16", cfg=cfg, d_iq=d_iq, outs=outs,
                          d_rd=d_rd, d_db=d_P, d_nseg=nseg, fp16=args.fp16, world=world))
-    if world == 1 and not args.no_extras and not args.fp16:
+    if full and world == 1 and not args.no_extras and not args.fp16:
         extra["fp16_storage"], leg16 = bench_fp16(eng, cfg, F, args, dev, stream, pmc)
         extra["config2_range_fft"], leg2 = bench_config2(eng, args, dev, stream, pmc)
         if not args.no_check:
@@ -420,7 +442,7 @@ def main():
     if rank == 0:
         # oracle leg, after every timed region: the CPU baseline on this run's own frames and the
         # full-size comparison of every timed frame's outputs with the float64 C oracle
-        cpu = cpu_baseline(args.cpu_seconds, d_iq, F, dt) if args.cpu_seconds > 0 and not legs else None
+        cpu = cpu_baseline(args.cpu_seconds, d_iq, F, dt) if full and args.cpu_seconds > 0 and not legs else None
         if legs:
             checked, cpu = oracle_leg(legs, args.cpu_seconds)
             ok = all(v.get("pass", False) for v in checked.values())
@@ -429,6 +451,7 @@ def main():
         line = {
             "metric": METRIC, "value": round(value, 1), "unit": "frames/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "full": full,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f16-storage/f32-compute" if args.fp16 else "f32",
             "data": "synthetic (SURVEY.md 8d generator, generated in HBM per rank)",
@@ -441,11 +464,13 @@ def main():
             "checked": checked,
             "stages_ms_per_step": {k: round(v[0], 4) for k, v in breakdown.items() if v[1]},
             "stages_note": "HIP-event pairs around every launch, 5 steps after the timed ones (the timed steps carry "
-                           "k_rdx's pair only)",
+                           "k_rdx's pair only)" if breakdown else None,
             "frames_with_target": det,
         }
         if fanout:
             line["input_fanout"] = fanout
+        if dumped:
+            line["dumped_outputs"] = dumped
         line.update(extra)
         print(json.dumps(line), flush=True)
     if world > 1:
@@ -513,6 +538,53 @@ def stft_leg(eng, form, slow, flist, d_len, C, win, fs, max_seg, d_P, pmax, nseg
     else:
         eng.stft_db_direct_device(slow, flist, d_len, C, win, STFT_WLEN, STFT_NOVERLAP, STFT_NFFT, fs, max_seg,
                                   pmax, d_P, d_halo=hbuf, n_halo=n_halo, d_halo_len=hl, stream=stream)
+
+
+DUMP_SEED = 0xD0F3
+DUMP_MAX_BYTES = 64 * 10 ** 6
+# per-array share of the 64 MB (bytes of float32): at 4096 frames the profile (16.8 MB), the slow-time rows
+# (4.2 MB) and the detections are whole; the RD map (8.6 GB) goes out as 8192 seeded (frame, range row)
+# Doppler rows plus 4 seeded whole frames, the STFT dB map (138 MB) as 68 k seeded segments
+DUMP_BUDGET = {"profile": 17 << 20, "slow_mag": 5 << 20, "tgt_count": 1 << 20, "tgt_range_idx": 1 << 20,
+               "tgt_range_mag": 1 << 20, "tgt_doppler_idx": 1 << 20, "rd_rows": 17 << 20, "rd_frames": 9 << 20,
+               "stft_db": 9 << 20}
+
+
+def _dump_rows(t, max_bytes: int, key: int):
+    """t as a float32 array if that fits max_bytes, else a fixed sample of its rows (dim 0): sorted row
+    indices drawn without replacement from a generator seeded by (DUMP_SEED, key) and the row count."""
+    import torch
+    rows = t.shape[0]
+    per = 4 * max(1, t[0].numel()) if rows else 4
+    n = min(rows, max_bytes // per)
+    if n < rows:
+        idx = np.sort(np.random.default_rng([DUMP_SEED, key]).choice(rows, size=n, replace=False))
+        t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+    return np.ascontiguousarray(t.float().cpu().numpy())
+
+
+def dump_outputs(path: str, outs, d_rd, d_db, d_nseg) -> dict:
+    """--dump-outputs: what the last timed step left in the caller's buffers, as <path>/<name>.npy
+    (float32): the per-frame outputs of fmcw_process_slow_device (profile, detections, slow-time
+    rows), the RD map as `rd_rows` ([F * Nr] rows of [Nd][re, im], sampled) and `rd_frames` (whole
+    frames, sampled), and the first nseg segments of the STFT dB map as `stft_db` (sampled), with
+    `stft_nseg` beside it.  Returns {name: shape} and the bytes written."""
+    os.makedirs(path, exist_ok=True)
+    nseg = int(d_nseg.item())
+    arrs = {k: outs[k] for k in ("profile", "slow_mag", "tgt_count", "tgt_range_idx", "tgt_range_mag",
+                                 "tgt_doppler_idx")}
+    arrs["rd_rows"] = d_rd.reshape((-1,) + tuple(d_rd.shape[2:]))
+    arrs["rd_frames"] = d_rd
+    arrs["stft_db"] = d_db[:nseg]
+    shapes, total = {}, 0
+    for key, (name, t) in enumerate(arrs.items()):
+        a = _dump_rows(t, DUMP_BUDGET[name], key)
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name], total = list(a.shape), total + a.nbytes
+    np.save(os.path.join(path, "stft_nseg.npy"), np.array([nseg], np.float64))
+    total += 8
+    assert total <= DUMP_MAX_BYTES, total
+    return {"dir": path, "bytes": total, "arrays": shapes}
 
 
 def sticky_check(eng, where: str) -> None:

@@ -7,6 +7,8 @@
   on outputs that agree with the oracle to fp32 rounding and fails on a
   perturbed RD map, range cube, detection or STFT.  The "device" outputs here
   are the Python oracle's own, rounded to float32, held in CPU tensors.
+* ``--full`` is off by default; ``--dump-outputs`` (dump_outputs) writes small
+  arrays whole and large ones as a fixed seeded sample of rows, within 64 MB.
 """
 import json
 import os
@@ -93,6 +95,64 @@ def test_world_size_must_match_gpus():
     r = _run_bench(["--gpus", "2", "--dry-dist"], env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode == 2
     assert "WORLD_SIZE 1" in r.stderr
+
+
+def test_full_is_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def _dump_case(F, NR, ND, C, nseg, seed=5):
+    g = np.random.default_rng(seed)
+    outs = {"profile": torch.from_numpy(g.random((F, NR), np.float32)),
+            "slow_mag": torch.from_numpy(g.random((F, C), np.float32)),
+            "tgt_count": torch.from_numpy(g.integers(0, 2, F).astype(np.int32)),
+            "tgt_range_idx": torch.from_numpy(g.integers(0, NR, (F, 1)).astype(np.int32)),
+            "tgt_range_mag": torch.from_numpy(g.random((F, 1), np.float32)),
+            "tgt_doppler_idx": torch.from_numpy(g.integers(0, ND, (F, 1)).astype(np.int32))}
+    d_rd = torch.from_numpy(g.random((F, NR, ND, 2), np.float32))
+    d_db = torch.from_numpy(g.random((F * C + 19, 33), np.float32))
+    return outs, d_rd, d_db, torch.tensor([nseg])
+
+
+def test_dump_outputs_small_arrays_are_whole(tmp_path):
+    """--dump-outputs: arrays under their share of the 64 MB are written whole, as float32, the dB map
+    cut at nseg; the fp16-storage RD map is widened, not reinterpreted."""
+    outs, d_rd, d_db, nseg = _dump_case(6, 32, 8, 16, 70)
+    info = bench.dump_outputs(str(tmp_path / "o"), outs, d_rd.half(), d_db, nseg)
+    got = {n: np.load(tmp_path / "o" / (n + ".npy")) for n in info["arrays"]}
+    for k, t in outs.items():
+        assert got[k].dtype == np.float32 and np.array_equal(got[k], t.numpy().astype(np.float32))
+    assert np.array_equal(got["rd_frames"], d_rd.half().float().numpy())
+    assert np.array_equal(got["rd_rows"], d_rd.half().float().numpy().reshape(6 * 32, 8, 2))
+    assert np.array_equal(got["stft_db"], d_db.numpy()[:70])
+    assert np.load(tmp_path / "o" / "stft_nseg.npy")[0] == 70
+    assert info["bytes"] == sum(a.nbytes for a in got.values()) + 8
+
+
+def test_dump_outputs_samples_large_arrays_within_budget(tmp_path, monkeypatch):
+    """Over its share an array goes out as a fixed seeded sample of its rows: the same rows on
+    every run, each row intact, and the total within the sum of the shares (< 64 MB)."""
+    assert sum(bench.DUMP_BUDGET.values()) + 8 <= bench.DUMP_MAX_BYTES == 64 * 10 ** 6
+    monkeypatch.setattr(bench, "DUMP_BUDGET", {k: (1 << 10) for k in bench.DUMP_BUDGET})
+    outs, d_rd, d_db, nseg = _dump_case(40, 32, 8, 16, 500)
+    a = bench.dump_outputs(str(tmp_path / "a"), outs, d_rd, d_db, nseg)
+    b = bench.dump_outputs(str(tmp_path / "b"), outs, d_rd, d_db, nseg)
+    assert a["arrays"] == b["arrays"] and a["bytes"] <= 9 * (1 << 10) + 8
+    for n, shape in a["arrays"].items():
+        x, y = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert x.dtype == np.float32 and list(x.shape) == shape and np.array_equal(x, y)
+    prof = np.load(tmp_path / "a" / "profile.npy")            # 8 of the 40 rows, in frame order, whole
+    full = outs["profile"].numpy()
+    rows = [int(np.nonzero((full == r).all(1))[0][0]) for r in prof]
+    assert prof.shape == (8, 32) and rows == sorted(set(rows))
+    db = np.load(tmp_path / "a" / "stft_db.npy")              # sampled from the first nseg segments only
+    src = d_db.numpy()[:500]
+    assert db.shape == (7, 33) and all((src == r).all(1).any() for r in db)
 
 
 def _config_small():

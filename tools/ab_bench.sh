@@ -5,6 +5,7 @@
 # value, ms per step, k_rdx us, outside-k_rdx ms, sclk, fp16 k_rdx us, config-2 K1 us.
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
+set -- --full "$@"    # the fp16, config-2 and checked columns of the summary come from the --full legs
 mkdir -p gpurun_out
 for r in ${ROUNDS:-1 2}; do for n in ${AB:-base new}; do
   # a name is a library (ab/<name>.so, cur = in-tree), optionally +VAR=value for one environment setting

@@ -3,7 +3,7 @@
 # bench.py exits non-zero on any k_rdx hand-off timeout (fmcw_synchronize after the timed steps) and on a
 # full-size check failure.  -> one line per run: frames/s, ms per step, k_rdx us (HIP events)
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-for v in "fp32" "fp16 --fp16"; do
+for v in "fp32 --full" "fp16 --full --fp16"; do   # --full: the full-size check runs after the soak
   set -- $v; n=$1; shift
   timeout -k 10 300 python3 -u bench.py --steps 2000 --warmup 10 --no-extras --cpu-seconds 0 "$@" > gpurun_out/soak_$n.log 2>&1
   rc=$?
