@@ -7,6 +7,7 @@
 // logspace/interp1 bin table of :293-299.
 #include "../../include/fmcw.h"
 #include "fmcw_internal.h"
+#include "xcd_ctr_plan.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -901,11 +902,15 @@ static int process_onepass(fmcw_ctx* c, const fmcw_params* p, const void* d_iq, 
     a.cand_rows = c->op_crows.as<float>();
     a.range_thr = p->range_thr; a.min_d = p->min_d; a.max_d = p->max_d; a.dist_per_bin = p->dist_per_bin;
     // counter sets: this launch counts in set x_ctr_set and zeroes the other one for the next launch (launches
-    // of a device run one at a time, launch_xcd's chain); FMCW_XCD_MEMSET=1: set 0 and a memset per launch
+    // of a device run one at a time, launch_xcd's chain); FMCW_XCD_MEMSET=1 (read per launch) adds a memset of
+    // the counting set and changes nothing else, so the knob may differ from one launch to the next
+    // (xcd_ctr_plan.h holds the rule, tests/native/xcd_ctr_plan.cpp checks it over every knob sequence)
     const bool xmemset = [] { const char* e = std::getenv("FMCW_XCD_MEMSET"); return e && e[0] == '1'; }();
+    const fmcw::XcdCtrPlan xp = fmcw::xcd_ctr_plan(c->x_ctr_set, xmemset);
     a.xcube = c->x_cube.as<float2>(); a.xerr = c->x_err.as<unsigned>();
-    a.xctr = c->x_ctr.as<unsigned>() + (xmemset ? 0 : c->x_ctr_set * fmcw::XCD_CTR_WORDS);
-    a.xclr = xmemset ? nullptr : c->x_ctr.as<unsigned>() + (1 - c->x_ctr_set) * fmcw::XCD_CTR_WORDS;
+    a.xctr = c->x_ctr.as<unsigned>() + xp.count_set * fmcw::XCD_CTR_WORDS;
+    a.xclr = xp.clear_set < 0 ? nullptr : c->x_ctr.as<unsigned>() + xp.clear_set * fmcw::XCD_CTR_WORDS;
+    a.xmemset = xp.memset_first ? 1 : 0;
 #ifdef FMCW_XCUBE_PAD_AB
     if (const char* e = std::getenv("FMCW_XCUBE_PAD")) {
       const size_t pad = std::min<size_t>((size_t)std::strtoull(e, nullptr, 0), (size_t)1 << 30) & ~(size_t)255;
@@ -931,7 +936,7 @@ static int process_onepass(fmcw_ctx* c, const fmcw_params* p, const void* d_iq, 
       {
         HIPCHK(fmcw::launch_xcd(a, s));
         c->xcd_used = true;
-        if (a.xclr && nf > 0) c->x_ctr_set ^= 1;   // the next launch counts in the set this one zeroed
+        if (nf > 0) c->x_ctr_set = xp.next_set;    // the next launch counts in the set this one zeroed
 #ifdef XK_SKEW
         {   // diagnostic build: the team's skew.  Per XCD and step j: the spread of the 32 members' publish
             // times of R(j - 1), and how long after the last publish each member's poll of it returned
@@ -1310,12 +1315,16 @@ int fmcw_stft_power_device(fmcw_ctx* c, const float* d_slow, const int32_t* d_li
   if (fmcw::stft_fast_path(wlen, a.hop)) {        // the reference's 20-tap window: W table + k_stft20
     int st = FMCW_OK;
     bool build = true;
-    float2* tab = fmcw::stft64_form(nfft) ? c->stft_tab64(s, d_win, nfft, &build, &st)
-                                          : c->stft_tab(s, (size_t)(nfft / 2 + 1) * 20 * 8, &st);
+    // the cached nfft-64 table only for the forms that tolerate a stale one; the table form (any other nfft,
+    // an unaligned d_P, FMCW_STFT_MFMA=0) gets a table built from this call's window (stft_tab clears the key)
+    const int mode = d_P ? 0 : 1;
+    float2* tab = fmcw::stft_form(a, mode, nullptr) != fmcw::STFT_FORM_TABLE
+                      ? c->stft_tab64(s, d_win, nfft, &build, &st)
+                      : c->stft_tab(s, (size_t)(nfft / 2 + 1) * 20 * 8, &st);
     CHK(st);
     if (build) HIPCHK(fmcw::launch_stft_table(d_win, nfft, tab, s));
     // device API: d_P is the caller's [max_seg][nfft/2+1] (fmcw.h), the table this stream's
-    HIPCHK(fmcw::launch_stft20(a, tab, d_P ? 0 : 1, nullptr, s, max_seg * (int64_t)(nfft / 2 + 1),
+    HIPCHK(fmcw::launch_stft20(a, tab, mode, nullptr, s, max_seg * (int64_t)(nfft / 2 + 1),
                                (int64_t)(nfft / 2 + 1) * 20));
     CHK(c->stft_tab_done(s));
   } else {
@@ -1349,8 +1358,10 @@ int fmcw_stft_db_direct_device(fmcw_ctx* c, const float* d_slow, const int32_t* 
   StageTimer tm(c, 5, s);
   int st = FMCW_OK;
   bool build = true;
-  float2* tab = fmcw::stft64_form(nfft) ? c->stft_tab64(s, d_win, nfft, &build, &st)
-                                        : c->stft_tab(s, (size_t)(nfft / 2 + 1) * 20 * 8, &st);
+  // as fmcw_stft_power_device: an unaligned d_out takes the table form, which must not see a cached table
+  float2* tab = fmcw::stft_form(a, 2, d_out) != fmcw::STFT_FORM_TABLE
+                    ? c->stft_tab64(s, d_win, nfft, &build, &st)
+                    : c->stft_tab(s, (size_t)(nfft / 2 + 1) * 20 * 8, &st);
   CHK(st);
   if (build) HIPCHK(fmcw::launch_stft_table(d_win, nfft, tab, s));
   HIPCHK(fmcw::launch_stft20(a, tab, 2, d_out, s, max_seg * (int64_t)(nfft / 2 + 1), (int64_t)(nfft / 2 + 1) * 20));

@@ -107,7 +107,7 @@ struct OnePassArgs {
                            // one 128-byte line per counter, XCD_CTR_WORDS in all (zero when a launch starts)
   unsigned* xclr;          // the context's other counter set (launches alternate between two): k_rdx's block 0
                            // zeroes its first XCD_IDLE words for the next launch, which saves a memset packet per
-                           // launch; nullptr: launch_xcd zeroes xctr before the launch (FMCW_XCD_MEMSET=1)
+                           // launch; nullptr: launch_xcd zeroes xctr before the launch
   unsigned* xerr;          // sticky, reported by fmcw_synchronize: bit 0 a hand-off wait timed out, bit 1 an XCD
                            // got more than 32 blocks (the launch's own abort word lets its grid drain; a later
                            // launch starts with a clear one)
@@ -116,6 +116,8 @@ struct OnePassArgs {
                            // are handed over as c32h (X / NR): no bin of the block can become a detection or
                            // slow-time candidate (host_s16mask in fmcw_api.cpp); 0 = every group c64
   int nteams;              // XCDs of the device (teams of 32 CUs): 8 in SPX mode, 1-4 in the partition modes
+  int xmemset;             // host only: 1 = launch_xcd zeroes xctr before the launch even though the previous
+                           // launch zeroed it (FMCW_XCD_MEMSET=1, xcd_ctr_plan.h)
   int8_t xcc_team[16];     // HW_REG_XCC_ID -> team index 0..nteams-1, -1 for an XCC not in the device
   const float2* xtab;      // XT_* sections (host, float64, lane order)
   float2 cal_sum;          // sum_{n < S} cal[n]
@@ -242,6 +244,13 @@ bool stft_fast_path(int wlen, int hop);
 // the nfft-64 matrix-core kernel (k_stft64m) serves this nfft (not disabled by FMCW_STFT_MFMA=0);
 // it verifies a cached W table against the call's window
 bool stft64_form(int nfft);
+// The kernel form launch_stft20 runs for (a, mode, dst): the nfft-64 kernels -- k_stft64f never reads the W
+// table, k_stft64m verifies it against the call's window, so both may be given a table cached from an earlier
+// call -- or the table form (k_stft_mfma / k_stft20), which trusts the table: its caller builds the table for
+// this call.  nfft-64 form, mode <= 2, no tiles, no table_form, a 16-byte aligned output (mode 1 has none);
+// FMCW_STFT64_FOLD=0 picks k_stft64m.
+enum StftForm { STFT_FORM_TABLE = 0, STFT_FORM_64F = 1, STFT_FORM_64M = 2 };
+StftForm stft_form(const StftArgs& a, int mode, const float* dst);
 hipError_t launch_stft_table(const float* win, int nfft, float2* tab, hipStream_t s);
 // dst_cap: floats available at dst (mode 0: at a.P), tab_cap: float2 entries of tab; a launch
 // whose writes would not fit returns hipErrorInvalidValue before anything is enqueued

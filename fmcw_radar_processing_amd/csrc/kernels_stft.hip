@@ -1008,6 +1008,16 @@ bool stft64_form(int nfft) {
   return nfft == 64 && !(mf && mf[0] == '0');
 }
 
+StftForm stft_form(const StftArgs& a, int mode, const float* dst) {
+  // k_stft64f / k_stft64m store 16 bytes per lane at out + 33 s0 (s0 a multiple of 64): an output
+  // that is not 16-byte aligned (a caller's slice) takes the table form, whose stores are 4 bytes
+  const float* outp = mode == 0 ? a.P : dst;
+  const bool out16 = mode == 1 || (reinterpret_cast<uintptr_t>(outp) & 15) == 0;
+  if (!(stft64_form(a.nfft) && mode >= 0 && mode <= 2 && !a.tiles && !a.table_form && out16)) return STFT_FORM_TABLE;
+  const char* fe = std::getenv("FMCW_STFT64_FOLD");
+  return fe && fe[0] == '0' ? STFT_FORM_64M : STFT_FORM_64F;
+}
+
 hipError_t launch_stft_table(const float* win, int nfft, float2* tab, hipStream_t s) {
   const int64_t n = (int64_t)(nfft / 2 + 1) * STFT_W;
   hipLaunchKernelGGL(k_stft_table, dim3(grid_for(n)), dim3(256), 0, s, win, nfft, tab);
@@ -1057,11 +1067,10 @@ hipError_t launch_stft20(const StftArgs& a, const float2* tab, int mode, float* 
   // nfft 64 (config 4): P / max(P) on the matrix cores, bit-identical (FMCW_STFT_MFMA=0: VALU)
   const char* mf = std::getenv("FMCW_STFT_MFMA");
   if ((mode == 4 || a.tiles) && mf && mf[0] == '0') return hipErrorInvalidValue;   // matrix-core form only
-  // k_stft64f / k_stft64m store 16 bytes per lane at out + 33 s0 (s0 a multiple of 64): an output
-  // that is not 16-byte aligned (a caller's slice) takes the table form, whose stores are 4 bytes
-  const float* outp = mode == 0 ? a.P : dst;
-  const bool out16 = mode == 1 || (reinterpret_cast<uintptr_t>(outp) & 15) == 0;
-  if (stft64_form(a.nfft) && mode <= 2 && !a.tiles && !a.table_form && out16) {
+  // the form is decided by stft_form alone: the API callers ask it too, before they decide whether the
+  // stream's cached nfft-64 table may be reused (only k_stft64f / k_stft64m tolerate a stale one)
+  const StftForm form = stft_form(a, mode, dst);
+  if (form != STFT_FORM_TABLE) {
     // persistent: a few blocks per CU loop over the tiles (nseg is on the device: the grid covers
     // max_seg's tiles at most, the blocks past the last tile return)
     int dev = 0;
@@ -1069,8 +1078,7 @@ hipError_t launch_stft20(const StftArgs& a, const float2* tab, int mode, float* 
     const int cus = device_cus(dev);
     int bpc = 3;
     if (const char* e = std::getenv("FMCW_STFT64_BPC")) bpc = std::max(1, std::min(16, std::atoi(e)));   // A/B
-    const char* fe = std::getenv("FMCW_STFT64_FOLD");
-    if (!(fe && fe[0] == '0')) {                  // the folded form (default; =0: k_stft64m, bit-identical to k_stft20)
+    if (form == STFT_FORM_64F) {                  // the folded form (default; FMCW_STFT64_FOLD=0: k_stft64m, bit-identical to k_stft20)
       // persistent: exactly the blocks that are resident at once (the occupancy query of each
       // instantiation, once): a grid past it runs its last blocks as a second round, which cost
       // the first form of this kernel 2x (3 resident blocks per CU against the 4 launched)

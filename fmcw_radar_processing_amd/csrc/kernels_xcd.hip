@@ -1211,8 +1211,9 @@ hipError_t launch_xcd(const OnePassArgs& a, hipStream_t s) {
     (void)hipGetLastError();
     if ((e = hipEventCreateWithFlags(&xcd_chain_ev[dev], hipEventDisableTiming | kEvDevice)) != hipSuccess) return e;
   }
-  // the counters start at zero: zeroed by the previous launch's block 0 (a.xclr of that launch), or here
-  if (!a.xclr)
+  // the counters start at zero: zeroed by the previous launch's block 0 (a.xclr of that launch), and here
+  // when the launch has no set to zero for its successor or FMCW_XCD_MEMSET=1 asks for the memset
+  if (!a.xclr || a.xmemset)
     if ((e = hipMemsetAsync(a.xctr, 0, sizeof(unsigned) * XCD_CTR_WORDS, s)) != hipSuccess) return e;
   if (a.nteams < 1 || a.nteams > 8) return hipErrorInvalidValue;
   const dim3 g(xk::NK * a.nteams), bl(64 * xk::NW);

@@ -177,24 +177,9 @@ def _run_fp16(eng, iq16, F, C, want_rd=True):
     return got
 
 
-# fp16 storage (BASELINE config 4 tolerance sweep): c32h IQ in, c32h RD out,
-# fp32 arithmetic, through the single pass.  SURVEY 8d: relative L2 <= 3e-3.
-# The hand-off under fp16 storage is c32h for the 128-bin blocks that hold no candidate-capable
-# bin (FMCW_S16=0: c64 everywhere); the slow rows come from fp32 values either way.
-@pytest.mark.parametrize("F,nts,fix,s16", [(3, 1024, False, True), (21, 1024, False, True), (9, 1000, False, True),
-                                           (10, 1024, True, True), (21, 1024, False, False)])
-def test_onepass_fp16_storage(onepass, monkeypatch, F, nts, fix, s16):
+def _check_fp16_vs_oracle(cfg, got, ref, wd, s16=True):
+    """The fp16-storage bars: ref is the oracle on the fp16-rounded input."""
     from tests.helpers import TOL_FP16_REL_L2, TOL_FP32_REL_L2
-    if fix:
-        monkeypatch.setenv("FMCW_ONEPASS_FORCE_FIX", "1")
-    if not s16:
-        monkeypatch.setenv("FMCW_S16", "0")
-    cfg, p, wr, wd, cal, iq = _frames(F, nts, frame0=700)
-    onepass.set_taps(cfg, cal, wr, wd)
-    iq16 = np.stack([iq.real, iq.imag], -1).astype(np.float16)
-    got = _run_fp16(onepass, iq16, F, 256)
-    x = iq16.astype(np.float32).view(np.complex64)[..., 0]
-    ref = O.process_frames(x, cal, p, wr, wd, want_cube=True, want_rd=True, rd_all_rows=True)
     assert rd_rel_err(got["rd"], ref["rd"], ref["cube"], wd, 256).max() <= TOL_FP16_REL_L2
     # the profile in the c32h hand-off blocks (away from the detection window) at the fp16-storage
     # bar, in the blocks around the window (fp32 hand-off) at the fp32 bar; slow rows and target
@@ -215,6 +200,26 @@ def test_onepass_fp16_storage(onepass, monkeypatch, F, nts, fix, s16):
     assert np.max(np.abs(got["tgt_range_mag"][m, 0] - ref["tgt_range_mag"][m, 0]) / ref["tgt_range_mag"][m, 0]) \
         <= TOL_FP32_REL_L2
     assert np.all(got["slow_mag"][~has] == 0)
+
+
+# fp16 storage (BASELINE config 4 tolerance sweep): c32h IQ in, c32h RD out,
+# fp32 arithmetic, through the single pass.  SURVEY 8d: relative L2 <= 3e-3.
+# The hand-off under fp16 storage is c32h for the 128-bin blocks that hold no candidate-capable
+# bin (FMCW_S16=0: c64 everywhere); the slow rows come from fp32 values either way.
+@pytest.mark.parametrize("F,nts,fix,s16", [(3, 1024, False, True), (21, 1024, False, True), (9, 1000, False, True),
+                                           (10, 1024, True, True), (21, 1024, False, False)])
+def test_onepass_fp16_storage(onepass, monkeypatch, F, nts, fix, s16):
+    if fix:
+        monkeypatch.setenv("FMCW_ONEPASS_FORCE_FIX", "1")
+    if not s16:
+        monkeypatch.setenv("FMCW_S16", "0")
+    cfg, p, wr, wd, cal, iq = _frames(F, nts, frame0=700)
+    onepass.set_taps(cfg, cal, wr, wd)
+    iq16 = np.stack([iq.real, iq.imag], -1).astype(np.float16)
+    got = _run_fp16(onepass, iq16, F, 256)
+    x = iq16.astype(np.float32).view(np.complex64)[..., 0]
+    ref = O.process_frames(x, cal, p, wr, wd, want_cube=True, want_rd=True, rd_all_rows=True)
+    _check_fp16_vs_oracle(cfg, got, ref, wd, s16)
 
 
 def test_onepass_fp16_matches_streams_fp16(engine):

@@ -218,7 +218,10 @@ def test_stft64_table_after_another_nfft_on_the_stream(engine, fold, monkeypatch
 def test_stft64_unaligned_output(engine, direct):
     """An output that is not 16-byte aligned (a caller's slice, fmcw.h sets no alignment rule for
     d_P / d_out) takes the table form instead of the 16-byte stores of k_stft64f / k_stft64m (ADVICE
-    r05): same dB as the aligned call within the fp32 bar, nothing written outside the slice."""
+    r05): same dB as the aligned call within the fp32 bar, nothing written outside the slice.  The
+    window does not change here; a window rewritten in place between unaligned calls (the table form
+    trusts its table, so the API must rebuild it) is
+    test_gpu_call_sequences.py::test_stft64_window_change_reaches_every_form."""
     import torch
     dev, s = "cuda", torch.cuda.current_stream()
     rng = np.random.default_rng(11)
