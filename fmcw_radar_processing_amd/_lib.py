@@ -20,7 +20,8 @@ FMCW_PIPE_AUTO, FMCW_PIPE_STREAMS, FMCW_PIPE_ONEPASS, FMCW_PIPE_XCD = 0, 1, 3, 4
 ABI_VERSION = 4
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_HIP", -3: "E_OOM", -4: "E_STATE", -5: "E_DATA"}
 STAGES = ("range", "doppler", "detect", "compact", "stft_power", "stft_db", "range_only", "range_doppler", "onepass",
-          "render")
+          "render", "cfar")
+FMCW_CFAR_LOCAL_MAX = 1
 
 
 class FmcwError(RuntimeError):
@@ -36,6 +37,15 @@ class Params(ct.Structure):
         ("max_targets", ct.c_int32), ("doppler_fallback_idx", ct.c_int32),
         ("if_scale", ct.c_float), ("range_thr", ct.c_float), ("doppler_thr", ct.c_float),
         ("min_d", ct.c_float), ("max_d", ct.c_float), ("dist_per_bin", ct.c_float),
+    ]
+
+
+class CfarParams(ct.Structure):
+    """fmcw_cfar_params (include/fmcw.h)."""
+    _fields_ = [
+        ("guard_r", ct.c_int32), ("guard_d", ct.c_int32), ("train_r", ct.c_int32), ("train_d", ct.c_int32),
+        ("r_lo", ct.c_int32), ("r_hi", ct.c_int32), ("max_det", ct.c_int32), ("flags", ct.c_int32),
+        ("alpha", ct.c_float),
     ]
 
 
@@ -86,6 +96,11 @@ SIGNATURES = {
     "fmcw_synchronize": (ct.c_int, [_P]),
     "fmcw_rdx_clock": (ct.c_int, [_P, ct.POINTER(_D), ct.POINTER(_D)]),
     "fmcw_copy_device": (ct.c_int, [_P, _P, _P, _I64, _P]),
+    "fmcw_cfar_check": (ct.c_int, [ct.POINTER(CfarParams), _I32, _I32, ct.POINTER(_I32)]),
+    "fmcw_cfar_alpha": (ct.c_int, [_I32, _D, ct.POINTER(_F)]),
+    "fmcw_cfar_device": (ct.c_int, [_P, ct.POINTER(CfarParams), _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P,
+                                    _P]),
+    "fmcw_cfar": (ct.c_int, [_P, ct.POINTER(CfarParams), _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "fmcw_json_write": (ct.c_int, [ct.c_char_p, ct.POINTER(JsonField), _I32, _I32, _I32, ct.POINTER(_I64)]),
     "fmcw_stft_png": (ct.c_int, [_P, _P, _I64, _P, _I32, _I32, _I32, _D, _I32, _P, _P, _P, ct.c_char_p, _I32, _I32,
                                  ct.POINTER(_I64)]),

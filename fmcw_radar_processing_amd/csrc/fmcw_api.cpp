@@ -177,7 +177,7 @@ void shard(int64_t total, int g, int world, int64_t& f0, int64_t& n) {
   n = base + (g < rem ? 1 : 0);
 }
 
-constexpr int kStages = 10;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render
+constexpr int kStages = 11;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar
 
 }  // namespace
 
@@ -320,6 +320,10 @@ struct fmcw_ctx {
   // k_detect_1p's arrival counter of the fused compaction (fmcw_process_slow_device), one per
   // stream; zeroed when allocated, reset by the kernel's last workgroup
   PerStream det_done;
+  // fmcw_cfar_device's per-wave detection lists and counts, one per stream
+  PerStream cfar_scr;
+  // fmcw_cfar (host pointers): the RD chunk, the per-frame outputs and the mask chunk on the device
+  DevBuf cf_in, cf_out, cf_mask;
   int64_t chunk_frames = 0;
   int64_t last_coarse_tiles = -1;     // tiles the last coarse-to-fine max(P) evaluated in full (diagnostics)
   int pipe_mode = FMCW_PIPE_AUTO;
@@ -2028,6 +2032,154 @@ int fmcw_synth_device(fmcw_ctx* c, const fmcw_params* p, int64_t frame0, int64_t
   a.cal = c->cal.as<float2>();
   HIPCHK(fmcw::launch_synth(a, pick(c, stream)));
   return FMCW_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// 2-D CA-CFAR over the RD map (kernels_cfar.hip)
+// ---------------------------------------------------------------------------
+static int cfar_check_impl(const fmcw_cfar_params* q, int32_t nr, int32_t nd, int32_t* n_train_full) {
+  if (!q) return fail(FMCW_E_ARG, "cfar params is NULL");
+  if (nr < 16 || nr > 2048 || (nr & (nr - 1))) return fail(FMCW_E_ARG, "cfar: nr must be a power of two in [16, 2048]");
+  if (nd < 4 || nd > 1024 || (nd & (nd - 1))) return fail(FMCW_E_ARG, "cfar: nd must be a power of two in [4, 1024]");
+  if (q->guard_r < 0 || q->guard_d < 0 || q->train_r < 0 || q->train_d < 0)
+    return fail(FMCW_E_ARG, "cfar: guard and training half-widths must be >= 0");
+  if (q->guard_r > 16 || q->guard_d > 16 || q->train_r > 16 || q->train_d > 16 || q->guard_r + q->train_r > 16 ||
+      q->guard_d + q->train_d > 16)
+    return fail(FMCW_E_ARG, "cfar: guard + train must be <= 16 in range (Wr) and in Doppler (Wd)");
+  if (q->train_r + q->train_d < 1) return fail(FMCW_E_ARG, "cfar: train_r + train_d must be >= 1");
+  const int Wr = q->guard_r + q->train_r, Wd = q->guard_d + q->train_d;
+  if (2 * Wd + 1 > nd) return fail(FMCW_E_ARG, "cfar: the Doppler window 2 Wd + 1 exceeds nd");
+  if (2 * Wr + 1 > nr) return fail(FMCW_E_ARG, "cfar: the range window 2 Wr + 1 exceeds nr");
+  if (!(q->alpha > 0.f) || !std::isfinite(q->alpha)) return fail(FMCW_E_ARG, "cfar: alpha must be finite and > 0");
+  if (q->r_lo > q->r_hi) return fail(FMCW_E_ARG, "cfar: r_lo > r_hi");
+  if (!(q->r_lo == 0 && q->r_hi == 0) && (q->r_lo < 1 || q->r_hi > nr))
+    return fail(FMCW_E_ARG, "cfar: the gate r_lo..r_hi must lie in 1..nr (or be 0, 0 for all rows)");
+  if (q->max_det < 1 || q->max_det > 1024) return fail(FMCW_E_ARG, "cfar: max_det must be in [1, 1024]");
+  if (q->flags & ~FMCW_CFAR_LOCAL_MAX) return fail(FMCW_E_ARG, "cfar: unknown flag bits");
+  if (n_train_full) *n_train_full = (2 * Wr + 1) * (2 * Wd + 1) - (2 * q->guard_r + 1) * (2 * q->guard_d + 1);
+  return FMCW_OK;
+}
+
+static int cfar_host_one(fmcw_ctx* c, const fmcw_cfar_params* q, const char* rd, int32_t dtype, int64_t F, int32_t nr,
+                         int32_t nd, int32_t* count, int32_t* ridx, int32_t* didx, float* power, float* noise,
+                         uint8_t* mask) {
+  CHK(set_device(c));
+  hipStream_t s = c->stream;
+  const int K = q->max_det;
+  const size_t fin = (size_t)nr * nd * esize(dtype), fmask = (size_t)nr * nd;
+  const int64_t Fc = host_chunk(fin, F);
+  Arena ar;
+  const size_t o_count = ar.add((size_t)F * 4), o_ridx = ar.add((size_t)F * K * 4), o_didx = ar.add((size_t)F * K * 4),
+               o_pow = ar.add((size_t)F * K * 4), o_noise = ar.add((size_t)F * K * 4);
+  CHK(c->cf_out.ensure(ar.off));
+  CHK(c->cf_in.ensure((size_t)Fc * fin));
+  if (mask) CHK(c->cf_mask.ensure((size_t)Fc * fmask));
+  char* const o = c->cf_out.as<char>();
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    const int64_t nf = std::min(Fc, F - f0);
+    HIPCHK(hipMemcpyAsync(c->cf_in.p, rd + (size_t)f0 * fin, (size_t)nf * fin, hipMemcpyHostToDevice, s));
+    CHK(fmcw_cfar_device(c, q, c->cf_in.p, dtype, nf, nr, nd, reinterpret_cast<int32_t*>(o + o_count) + f0,
+                         reinterpret_cast<int32_t*>(o + o_ridx) + f0 * K, reinterpret_cast<int32_t*>(o + o_didx) + f0 * K,
+                         reinterpret_cast<float*>(o + o_pow) + f0 * K, reinterpret_cast<float*>(o + o_noise) + f0 * K,
+                         mask ? c->cf_mask.as<uint8_t>() : nullptr, s));
+    if (mask) HIPCHK(hipMemcpyAsync(mask + (size_t)f0 * fmask, c->cf_mask.p, (size_t)nf * fmask, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));           // the chunk buffers are reused by the next chunk
+  }
+  HIPCHK(hipMemcpyAsync(count, o + o_count, (size_t)F * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(ridx, o + o_ridx, (size_t)F * K * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(didx, o + o_didx, (size_t)F * K * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(power, o + o_pow, (size_t)F * K * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(noise, o + o_noise, (size_t)F * K * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return FMCW_OK;
+}
+
+extern "C" {
+
+int fmcw_cfar_check(const fmcw_cfar_params* q, int32_t nr, int32_t nd, int32_t* n_train_full) {
+  return cfar_check_impl(q, nr, nd, n_train_full);
+}
+
+int fmcw_cfar_alpha(int32_t n_train, double pfa, float* alpha) {
+  if (!alpha) return fail(FMCW_E_ARG, "alpha is NULL");
+  if (n_train < 1) return fail(FMCW_E_ARG, "cfar: n_train must be >= 1");
+  if (!(pfa > 0.0 && pfa < 1.0)) return fail(FMCW_E_ARG, "cfar: pfa must be in (0, 1)");
+  *alpha = (float)((double)n_train * std::expm1(-std::log(pfa) / (double)n_train));   // N (pfa^(-1/N) - 1)
+  return FMCW_OK;
+}
+
+int fmcw_cfar_device(fmcw_ctx* c, const fmcw_cfar_params* q, const void* d_rd, int32_t rd_dtype, int64_t F, int32_t nr,
+                     int32_t nd, int32_t* d_count, int32_t* d_ridx, int32_t* d_didx, float* d_power, float* d_noise,
+                     uint8_t* d_mask, void* stream) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(cfar_check_impl(q, nr, nd, nullptr));
+  if (rd_dtype != FMCW_C64 && rd_dtype != FMCW_C32H) return fail(FMCW_E_ARG, "bad rd_dtype");
+  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
+  if (F == 0) return FMCW_OK;
+  if (!d_rd || !d_count || !d_ridx || !d_didx || !d_power || !d_noise) return fail(FMCW_E_ARG, "required pointer is NULL");
+  if (reinterpret_cast<uintptr_t>(d_rd) & 15) return fail(FMCW_E_ARG, "cfar: d_rd must be 16-byte aligned");
+  CHK(set_device(c));
+  hipStream_t s = pick(c, stream);
+  fmcw::CfarArgs a{};
+  a.h = rd_dtype == FMCW_C32H;
+  a.scale = a.h ? (float)nr * (float)nd : 1.f;
+  a.NR = nr; a.ND = nd;
+  a.gr = q->guard_r; a.gd = q->guard_d; a.tr = q->train_r; a.td = q->train_d;
+  a.g0 = q->r_lo == 0 ? 0 : q->r_lo - 1;
+  a.g1 = q->r_hi == 0 ? nr - 1 : q->r_hi - 1;
+  a.K = q->max_det;
+  a.local_max = (q->flags & FMCW_CFAR_LOCAL_MAX) ? 1 : 0;
+  a.alpha = q->alpha;
+  fmcw::cfar_plan(a, F);
+  // frames per launch pair: at most 256 MiB of list scratch (the lists hold max_det entries per wave;
+  // FMCW_CFAR_SCRATCH, in bytes, overrides, for tests of the launch seams)
+  const size_t per = fmcw::cfar_scratch_per_frame(a);
+  size_t budget = (size_t)256 << 20;
+  if (const char* e = std::getenv("FMCW_CFAR_SCRATCH"); e && std::atoll(e) > 0) budget = (size_t)std::atoll(e);
+  const int64_t Fc = std::max<int64_t>(1, std::min<int64_t>({F, (int64_t)(budget / per), (int64_t)32768}));
+  const size_t nsub = (size_t)a.strips * a.tiles * a.waves;
+  const size_t list_bytes = (size_t)Fc * nsub * a.K * sizeof(float4);
+  int st = FMCW_OK;
+  char* scr = static_cast<char*>(c->cfar_scr.get(s, list_bytes + (size_t)Fc * nsub * 4, &st));
+  CHK(st);
+  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    a.F = std::min(Fc, F - f0);
+    a.rd = static_cast<const char*>(d_rd) + (size_t)f0 * fin;
+    a.sub_list = reinterpret_cast<float4*>(scr);
+    a.sub_count = reinterpret_cast<int32_t*>(scr + list_bytes);
+    a.det_count = d_count + f0;
+    a.det_ridx = d_ridx + f0 * a.K;
+    a.det_didx = d_didx + f0 * a.K;
+    a.det_power = d_power + f0 * a.K;
+    a.det_noise = d_noise + f0 * a.K;
+    a.mask = d_mask ? d_mask + (size_t)f0 * nr * nd : nullptr;
+    StageTimer tm(c, 10, s);
+    HIPCHK(fmcw::launch_cfar(a, s));
+    tm.done();
+  }
+  CHK(c->cfar_scr.done(s));
+  return FMCW_OK;
+}
+
+int fmcw_cfar(fmcw_ctx* c, const fmcw_cfar_params* q, const void* rd, int32_t rd_dtype, int64_t F, int32_t nr, int32_t nd,
+              int32_t* count, int32_t* ridx, int32_t* didx, float* power, float* noise, uint8_t* mask) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(cfar_check_impl(q, nr, nd, nullptr));
+  if (rd_dtype != FMCW_C64 && rd_dtype != FMCW_C32H) return fail(FMCW_E_ARG, "bad rd_dtype");
+  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
+  if (F == 0) return FMCW_OK;
+  if (!rd || !count || !ridx || !didx || !power || !noise) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
+  const int K = q->max_det;
+  // frames are independent: contiguous shards, each written in place
+  return over_devices(c, F, [&](fmcw_ctx* d, int, int64_t f0, int64_t n) {
+    return cfar_host_one(d, q, static_cast<const char*>(rd) + (size_t)f0 * fin, rd_dtype, n, nr, nd, count + f0,
+                         ridx + f0 * K, didx + f0 * K, power + f0 * K, noise + f0 * K,
+                         mask ? mask + (size_t)f0 * nr * nd : nullptr);
+  });
 }
 
 }  // extern "C"

@@ -294,6 +294,32 @@ hipError_t launch_fill_u32(uint32_t* p, uint32_t v, int64_t n, hipStream_t s);
 hipError_t launch_copy16(const void* src, void* dst, int64_t bytes, hipStream_t s);
 
 
+// 2-D CA-CFAR over the RD map (kernels_cfar.hip): k_cfar + k_cfar_gather
+struct CfarArgs {
+  const void* rd;          // [F][NR][ND] c64, or c32h (h) holding D / (NR ND); 16-byte aligned
+  int h;
+  float scale;             // NR * ND when h, else 1: powers come out in the units of |D|^2
+  int64_t F;
+  int NR, ND;
+  int gr, gd, tr, td;      // guard / training half-widths
+  int g0, g1;              // gated rows, 0-based, inclusive
+  int K, local_max;
+  float alpha;
+  int RS, strips;          // rows per strip, strips over [g0, g1]          (cfar_plan)
+  int TC, tiles, waves;    // columns per tile, tiles per row, waves per workgroup
+  int32_t* sub_count;      // scratch [F][strips * tiles * waves] detections of each wave's cells
+  float4* sub_list;        // scratch [F][strips * tiles * waves][K] {cell index bits, P, S / N, 0}
+  int32_t* det_count;      // [F]
+  int32_t* det_ridx;       // [F][K]
+  int32_t* det_didx;       // [F][K]
+  float* det_power;        // [F][K]
+  float* det_noise;        // [F][K]
+  uint8_t* mask;           // [F][NR][ND] or nullptr
+};
+void cfar_plan(CfarArgs& a, int64_t F);
+size_t cfar_scratch_per_frame(const CfarArgs& a);
+hipError_t launch_cfar(const CfarArgs& a, hipStream_t s);
+
 bool range_size_supported(int nr);
 bool doppler_size_supported(int nd);
 

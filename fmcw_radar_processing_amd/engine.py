@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import FMCW_C32H, FMCW_C64, STAGES, FmcwError, check
-from .params import FmcwConfig
+from .params import CfarConfig, FmcwConfig
 
 
 def _ptr(a) -> ct.c_void_p:
@@ -241,6 +241,61 @@ class Engine:
         with _sided(stream) as hs:
             check(self.lib.fmcw_synth_device(self.h, ct.byref(self.p), int(frame0), int(F), _ptr(d_iq), dtype,
                                              hs))
+
+    # ---- 2-D CA-CFAR over the RD map (include/fmcw.h, fmcw_cfar_params) ---------
+    def cfar(self, rd: np.ndarray, q: CfarConfig, want_mask: bool = False) -> dict:
+        """Detections of rd: complex64 [F][nr][nd], or float16 [F][nr][nd][2] holding D / (nr nd).
+        Host arrays, sharded over the context's devices.  Returns det_count [F], det_range_idx,
+        det_doppler_idx, det_power, det_noise [F][max_det] (1-based indices, 0 where unused) and,
+        once set_taps has given the geometry's scales, range_m / speed_mps of every listed
+        detection (NaN where unused); `mask` [F][nr][nd] uint8 when asked for."""
+        if rd.dtype == np.complex64 and rd.ndim == 3:
+            rd, dt = np.ascontiguousarray(rd), FMCW_C64
+        elif rd.dtype == np.float16 and rd.ndim == 4 and rd.shape[-1] == 2:
+            rd, dt = np.ascontiguousarray(rd), FMCW_C32H
+        else:
+            raise TypeError("rd must be complex64 [F][nr][nd] or float16 [F][nr][nd][2]")
+        F, nr, nd = rd.shape[:3]
+        K = int(q.max_det)
+        out = dict(det_count=np.zeros(F, np.int32), det_range_idx=np.zeros((F, max(K, 0)), np.int32),
+                   det_doppler_idx=np.zeros((F, max(K, 0)), np.int32), det_power=np.zeros((F, max(K, 0)), np.float32),
+                   det_noise=np.zeros((F, max(K, 0)), np.float32))
+        mask = np.zeros((F, nr, nd), np.uint8) if want_mask else None
+        qa = q.abi()
+        check(self.lib.fmcw_cfar(self.h, ct.byref(qa), _ptr(rd), dt, F, nr, nd, _ptr(out["det_count"]),
+                                 _ptr(out["det_range_idx"]), _ptr(out["det_doppler_idx"]), _ptr(out["det_power"]),
+                                 _ptr(out["det_noise"]), _ptr(mask)))
+        if mask is not None:
+            out["mask"] = mask
+        if self.cfg is not None and (self.cfg.nr, self.cfg.nd) == (nr, nd):
+            used = out["det_range_idx"] > 0
+            out["range_m"] = np.where(used, self.cfg.range_m(out["det_range_idx"]), np.nan)
+            out["speed_mps"] = np.where(used, self.cfg.speed(out["det_doppler_idx"]), np.nan)
+        return out
+
+    def cfar_device(self, q: CfarConfig, d_rd, rd_dtype: int, F: int, nr: int, nd: int, outs: dict, d_mask=None,
+                    stream=None) -> None:
+        """fmcw_cfar_device: d_rd [F][nr][nd] of rd_dtype on the device; outs holds the device
+        buffers det_count [F] int32, det_range_idx / det_doppler_idx [F][max_det] int32 and
+        det_power / det_noise [F][max_det] float32.  Asynchronous on `stream`."""
+        qa = q.abi()
+        with _sided(stream) as hs:
+            check(self.lib.fmcw_cfar_device(self.h, ct.byref(qa), _ptr(d_rd), int(rd_dtype), int(F), int(nr), int(nd),
+                                            _ptr(outs["det_count"]), _ptr(outs["det_range_idx"]),
+                                            _ptr(outs["det_doppler_idx"]), _ptr(outs["det_power"]),
+                                            _ptr(outs["det_noise"]), _ptr(d_mask), hs))
+
+    def process_cfar_device(self, d_iq, F: int, in_dtype: int, outs: dict, q: CfarConfig, d_rd, cfar_outs: dict,
+                            out_dtype: int = FMCW_C64, d_mask=None, d_cube=None, probe_column: int = 0,
+                            stream=None) -> None:
+        """IQ in, detections out, on one stream with no host round trip: process_device writing the
+        RD map to d_rd (out_dtype), then cfar_device over it."""
+        cfg = self._need()
+        if d_rd is None:
+            raise ValueError("process_cfar_device needs an RD buffer")
+        self.process_device(d_iq, F, in_dtype, outs, d_cube=d_cube, d_rd=d_rd, out_dtype=out_dtype,
+                            probe_column=probe_column, stream=stream)
+        self.cfar_device(q, d_rd, out_dtype, F, cfg.nr, cfg.nd, cfar_outs, d_mask=d_mask, stream=stream)
 
     # ---- timing -----------------------------------------------------------------
     def timing(self, level: int) -> None:

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import windows
-from ._lib import Params
+from ._lib import FMCW_CFAR_LOCAL_MAX, CfarParams, Params
 
 C0 = 3e8  # radar_processing.m:67
 
@@ -110,6 +110,58 @@ class FmcwConfig:
         if self.mode == PARITY:
             return windows.kaiser(self.window_length, 3.0)   # :276 kaiser(window_length, 3)
         return windows.hann(self.window_length)              # config 4: Hann(20)
+
+
+@dataclass
+class CfarConfig:
+    """fmcw_cfar_params (include/fmcw.h): 2-D cell-averaging CFAR over the RD map.  Half-widths in
+    cells; the gate r_lo..r_hi is 1-based and inclusive, (0, 0) = every row; alpha is the linear
+    power ratio of the test P > alpha * S / N."""
+    guard_r: int = 1
+    guard_d: int = 1
+    train_r: int = 2
+    train_d: int = 2
+    alpha: float = 1.0
+    r_lo: int = 0
+    r_hi: int = 0
+    max_det: int = 64
+    local_max: bool = False
+
+    @property
+    def n_train_full(self) -> int:
+        wr, wd = self.guard_r + self.train_r, self.guard_d + self.train_d
+        return (2 * wr + 1) * (2 * wd + 1) - (2 * self.guard_r + 1) * (2 * self.guard_d + 1)
+
+    def abi(self) -> CfarParams:
+        return CfarParams(self.guard_r, self.guard_d, self.train_r, self.train_d, self.r_lo, self.r_hi, self.max_det,
+                          FMCW_CFAR_LOCAL_MAX if self.local_max else 0, self.alpha)
+
+    @staticmethod
+    def alpha_for(n_train: int, pfa: float) -> float:
+        """fmcw_cfar_alpha: N (pfa^(-1/N) - 1), as the float32 the C-ABI carries."""
+        import ctypes as ct
+
+        from . import _lib
+        a = ct.c_float()
+        _lib.check(_lib.load().fmcw_cfar_alpha(int(n_train), float(pfa), ct.byref(a)))
+        return float(a.value)
+
+    @classmethod
+    def for_config(cls, cfg: "FmcwConfig", pfa: float = 1e-3, guard=(1, 1), train=(2, 2), max_det: int = 64,
+                   local_max: bool = False) -> "CfarConfig":
+        """The detector for cfg's RD map: the gate is the peak rule's (:211, f_search_peak), the
+        1-based bins i in 2..nr-1 with (i - 1) * dist_per_bin in [min_d, max_d]; alpha is the
+        cell-averaging value for pfa with the full window's training-cell count."""
+        q = cls(guard_r=int(guard[0]), guard_d=int(guard[1]), train_r=int(train[0]), train_d=int(train[1]),
+                max_det=int(max_det), local_max=bool(local_max))
+        i = np.arange(2, cfg.nr)
+        d = (i - 1) * cfg.dist_per_bin
+        sel = i[(d >= cfg.min_d) & (d <= cfg.max_d)]
+        if len(sel) == 0:
+            raise ValueError("no range bin lies in [min_d, max_d]")
+        q.r_lo, q.r_hi = int(sel[0]), int(sel[-1])
+        q.alpha = cls.alpha_for(q.n_train_full, pfa)
+        return q
 
 
 def derive_params(device: dict, nr: int = 256, nd: int = 16, mode: str = PARITY, **over) -> FmcwConfig:

@@ -39,7 +39,9 @@ extern "C" {
 #endif
 
 /* 3: FMCW_PIPE_ONEPASS names the XCD-team schedule (E_ARG where the XCD census fails),
- *    fmcw_default_devices, FMCW_JSON_BOOL */
+ *    fmcw_default_devices, FMCW_JSON_BOOL
+ * 4: + the CFAR entry points (fmcw_cfar_check, fmcw_cfar_alpha, fmcw_cfar_device, fmcw_cfar)
+ *    and timing stage 10, added within ABI 4: nothing that existed changed */
 #define FMCW_ABI_VERSION 4
 
 typedef enum fmcw_status {
@@ -264,7 +266,8 @@ int fmcw_synth_device(fmcw_ctx* ctx, const fmcw_params* p, int64_t frame0, int64
  * timed run (each event pair costs the stream a few microseconds).
  * stage: 0 range, 1 doppler, 2 detect, 3 compact, 4 stft_power, 5 stft_db,
  *        6 range_only, 7 range+Doppler span, 8 k_rdx (single-pass schedule,
- *        level 2), 9 render (spectrogram.png).  fmcw_timing_read synchronises. */
+ *        level 2), 9 render (spectrogram.png), 10 cfar (one pair per k_cfar + k_cfar_gather
+ *        launch pair of fmcw_cfar_device).  fmcw_timing_read synchronises. */
 int fmcw_timing_enable(fmcw_ctx* ctx, int32_t enable);
 int fmcw_timing_read(fmcw_ctx* ctx, int32_t stage, double* total_ms, int64_t* launches);
 int fmcw_timing_reset(fmcw_ctx* ctx);
@@ -309,6 +312,64 @@ int fmcw_synchronize(fmcw_ctx* ctx);
  *   pointers), asynchronous on `stream`: the HBM copy ceiling of k_rdx's bytes (bench.py). */
 int fmcw_rdx_clock(fmcw_ctx* ctx, double* mhz, double* us);
 int fmcw_copy_device(fmcw_ctx* ctx, const void* d_src, void* d_dst, int64_t bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * 2-D cell-averaging CFAR over the range-Doppler map (added within ABI 4; beyond the
+ * reference, whose only consumer of the map is the one-peak rule of :211 / :233).
+ * Indices below are 0-based; every index the calls return is 1-based.
+ *   rd [F][nr][nd]   the layout fmcw_process* writes: FMCW_C64, or FMCW_C32H (values
+ *                    D/(nr*nd)); nr a power of two in 16..2048, nd one in 4..1024.
+ *                    P[r][d] = re^2 + im^2 of the stored value.
+ *   Training set of cell (r, d), with Wr = guard_r + train_r, Wd = guard_d + train_d:
+ *     the cells (r + dr, (d + dd) mod nd) with |dr| <= Wr, |dd| <= Wd, not
+ *     (|dr| <= guard_r and |dd| <= guard_d), and 0 <= r + dr < nr.  Doppler is circular,
+ *     range is clipped: N(r) cells remain, S is the sum of P over them (formed by
+ *     additions only, so relative error <= (N - 1) 2^-24).
+ *   Test: a gated cell is a detection iff P > alpha * S / N.
+ *   FMCW_CFAR_LOCAL_MAX: it must also be the maximum of its 3 x 3 neighbourhood (circular
+ *     in Doppler, clipped in range, gated or not): P > the four neighbours before it in
+ *     raster order, P >= the four after it, so a two-cell plateau keeps one cell.
+ *   Constraints: guards, trains >= 0; train_r + train_d >= 1; Wr, Wd <= 16;
+ *     2 Wr + 1 <= nr; 2 Wd + 1 <= nd; alpha > 0; 1 <= r_lo <= r_hi <= nr or r_lo = r_hi = 0
+ *     (all rows); max_det in 1..1024.
+ *   Outputs per frame (K = max_det):
+ *     det_count [F] i32          detections found; may exceed K (the list was cut)
+ *     det_range_idx, det_doppler_idx [F][K] i32   1-based, ascending (range, doppler); the
+ *                                first K in that order; 0 where unused
+ *     det_power, det_noise [F][K] f32   P and S/N in the units of |range_Doppler_tx1rx1|^2
+ *                                (fp16 storage: times (nr*nd)^2, exact); 0 where unused
+ *     mask [F][nr][nd] u8 or NULL   1 where a cell is a detection; not cut at K
+ *   Results are bit-identical from call to call and do not depend on F.
+ * ------------------------------------------------------------------------- */
+enum { FMCW_CFAR_LOCAL_MAX = 1 };
+typedef struct fmcw_cfar_params {
+  int32_t guard_r, guard_d, train_r, train_d;
+  int32_t r_lo, r_hi;      /* 1-based inclusive gate, 0/0 = all rows */
+  int32_t max_det;         /* 1..1024 */
+  int32_t flags;           /* FMCW_CFAR_LOCAL_MAX */
+  float   alpha;           /* linear power ratio, > 0 */
+} fmcw_cfar_params;
+
+/* Host only, no context.  fmcw_cfar_check: FMCW_E_ARG (with a message) for any violation of
+ * the constraints above; on success *n_train_full (may be NULL) = the full window's
+ * training-cell count (2Wr+1)(2Wd+1) - (2 guard_r+1)(2 guard_d+1).
+ * fmcw_cfar_alpha: alpha = N (pfa^(-1/N) - 1), the cell-averaging rule for exponentially
+ * distributed noise power; FMCW_E_ARG unless 0 < pfa < 1 and n_train >= 1. */
+int fmcw_cfar_check(const fmcw_cfar_params* q, int32_t nr, int32_t nd, int32_t* n_train_full);
+int fmcw_cfar_alpha(int32_t n_train, double pfa, float* alpha);
+
+/* Device pointers (d_rd 16-byte aligned), asynchronous on `stream`; needs no fmcw_set_taps.
+ * Acts on the context's first device. */
+int fmcw_cfar_device(fmcw_ctx* ctx, const fmcw_cfar_params* q, const void* d_rd, int32_t rd_dtype,
+                     int64_t F, int32_t nr, int32_t nd, int32_t* d_det_count,
+                     int32_t* d_det_range_idx, int32_t* d_det_doppler_idx, float* d_det_power,
+                     float* d_det_noise, uint8_t* d_mask, void* stream);
+
+/* Host pointers: staged through context memory, frames sharded over the context's devices
+ * (bit-identical shards); returns when the outputs are on the host. */
+int fmcw_cfar(fmcw_ctx* ctx, const fmcw_cfar_params* q, const void* rd, int32_t rd_dtype, int64_t F,
+              int32_t nr, int32_t nd, int32_t* det_count, int32_t* det_range_idx,
+              int32_t* det_doppler_idx, float* det_power, float* det_noise, uint8_t* mask);
 
 /* ---------------------------------------------------------------------------
  * spectrogram.png, replacing radar_processing.m:331-348:

@@ -22,6 +22,11 @@
  *   bytes = fmcw_mex('json', path, s)                             -> fmcw_json_write (:313-321 and the other
  *                                        jsonencode(s, 'PrettyPrint', true) + fprintf writes); s: a scalar
  *                                        struct of char rows and double / single / int32 arrays
+ *   [cnt, ridx, didx, power, noise] = fmcw_mex('cfar', Q, rd)     -> fmcw_cfar: 2-D CA-CFAR over an RD map
+ *                                        (beyond the reference); Q: a struct with the fields of
+ *                                        fmcw_cfar_params; rd: single complex Nd x Nr x F (the C array
+ *                                        [F][Nr][Nd]: permute(range_Doppler, [2 1 3])); ridx ... noise are
+ *                                        max_det x F
  *   fmcw_mex('close')                                             -> fmcw_ctx_destroy
  *
  * P is a struct with the fields of fmcw_params (nts, pn, nr, nd, max_targets,
@@ -222,6 +227,37 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     else
       check(fmcw_stft(g_ctx, x, L, w, wlen, nov, nfft, fs, nlog, mxGetSingles(plhs[0]), mxGetSingles(plhs[1]),
                       mxGetSingles(plhs[2])));
+    return;
+  }
+  if (!strcmp(cmd, "cfar")) {               /* [cnt, ridx, didx, power, noise] = fmcw_mex('cfar', Q, rd) */
+    if (nrhs != 3) mexErrMsgIdAndTxt("fmcw:arg", "cfar: Q, rd");
+    const mxArray* s = prhs[1];
+    const mxArray* rd = prhs[2];
+    if (!mxIsStruct(s)) mexErrMsgIdAndTxt("fmcw:arg", "Q must be a struct");
+    fmcw_cfar_params q;
+    q.guard_r = (int32_t)field(s, "guard_r");
+    q.guard_d = (int32_t)field(s, "guard_d");
+    q.train_r = (int32_t)field(s, "train_r");
+    q.train_d = (int32_t)field(s, "train_d");
+    q.r_lo = (int32_t)field(s, "r_lo");
+    q.r_hi = (int32_t)field(s, "r_hi");
+    q.max_det = (int32_t)field(s, "max_det");
+    q.flags = (int32_t)field(s, "flags");
+    q.alpha = (float)field(s, "alpha");
+    if (!mxIsSingle(rd) || !mxIsComplex(rd) || mxGetNumberOfDimensions(rd) < 2)
+      mexErrMsgIdAndTxt("fmcw:arg", "rd must be single complex Nd x Nr x F");
+    const mwSize* dims = mxGetDimensions(rd);
+    const int64_t F = mxGetNumberOfDimensions(rd) >= 3 ? (int64_t)dims[2] : 1;
+    const int32_t nd = (int32_t)dims[0], nr = (int32_t)dims[1];
+    check(fmcw_cfar_check(&q, nr, nd, NULL));   /* before max_det sizes the outputs */
+    const mwSize K = (mwSize)q.max_det;
+    plhs[0] = mxCreateNumericMatrix(1, F, mxINT32_CLASS, mxREAL);    /* detections found per frame */
+    plhs[1] = mxCreateNumericMatrix(K, F, mxINT32_CLASS, mxREAL);    /* range index, 1-based, 0 = unused */
+    plhs[2] = mxCreateNumericMatrix(K, F, mxINT32_CLASS, mxREAL);    /* Doppler index */
+    plhs[3] = mxCreateNumericMatrix(K, F, mxSINGLE_CLASS, mxREAL);   /* |D|^2 of the cell */
+    plhs[4] = mxCreateNumericMatrix(K, F, mxSINGLE_CLASS, mxREAL);   /* noise estimate S / N */
+    check(fmcw_cfar(g_ctx, &q, mxGetComplexSingles(rd), FMCW_C64, F, nr, nd, mxGetInt32s(plhs[0]), mxGetInt32s(plhs[1]),
+                    mxGetInt32s(plhs[2]), mxGetSingles(plhs[3]), mxGetSingles(plhs[4]), NULL));
     return;
   }
   mexErrMsgIdAndTxt("fmcw:arg", "unknown command '%s'", cmd);
