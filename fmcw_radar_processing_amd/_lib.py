@@ -22,6 +22,7 @@ STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_HIP", -3: "E_OOM", -4: "E_STATE", -
 STAGES = ("range", "doppler", "detect", "compact", "stft_power", "stft_db", "range_only", "range_doppler", "onepass",
           "render", "cfar")
 FMCW_CFAR_LOCAL_MAX = 1
+FMCW_SIG_DB = 1
 
 
 class FmcwError(RuntimeError):
@@ -46,6 +47,14 @@ class CfarParams(ct.Structure):
         ("guard_r", ct.c_int32), ("guard_d", ct.c_int32), ("train_r", ct.c_int32), ("train_d", ct.c_int32),
         ("r_lo", ct.c_int32), ("r_hi", ct.c_int32), ("max_det", ct.c_int32), ("flags", ct.c_int32),
         ("alpha", ct.c_float),
+    ]
+
+
+class SigParams(ct.Structure):
+    """fmcw_sig_params (include/fmcw.h)."""
+    _fields_ = [
+        ("r_lo", ct.c_int32), ("r_hi", ct.c_int32), ("track_half", ct.c_int32), ("dc_half", ct.c_int32),
+        ("flags", ct.c_int32), ("floor_db", ct.c_float),
     ]
 
 
@@ -101,6 +110,10 @@ SIGNATURES = {
     "fmcw_cfar_device": (ct.c_int, [_P, ct.POINTER(CfarParams), _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P,
                                     _P]),
     "fmcw_cfar": (ct.c_int, [_P, ct.POINTER(CfarParams), _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "fmcw_sig_check": (ct.c_int, [ct.POINTER(SigParams), _I32, _I32]),
+    "fmcw_sig_device": (ct.c_int, [_P, ct.POINTER(SigParams), _P, _I32, _I64, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P]),
+    "fmcw_sig_db_device": (ct.c_int, [_P, _P, _I64, _P, _F, _P, _P]),
+    "fmcw_sig": (ct.c_int, [_P, ct.POINTER(SigParams), _P, _I32, _I64, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
     "fmcw_json_write": (ct.c_int, [ct.c_char_p, ct.POINTER(JsonField), _I32, _I32, _I32, ct.POINTER(_I64)]),
     "fmcw_stft_png": (ct.c_int, [_P, _P, _I64, _P, _I32, _I32, _I32, _D, _I32, _P, _P, _P, ct.c_char_p, _I32, _I32,
                                  ct.POINTER(_I64)]),

@@ -324,6 +324,10 @@ struct fmcw_ctx {
   PerStream cfar_scr;
   // fmcw_cfar (host pointers): the RD chunk, the per-frame outputs and the mask chunk on the device
   DevBuf cf_in, cf_out, cf_mask;
+  // fmcw_sig_device's per-slab column sums, one per stream
+  PerStream sig_scr;
+  // fmcw_sig (host pointers): the RD chunk, the centres, and both maps with their two maxima on the device
+  DevBuf sg_in, sg_ctr, sg_out;
   int64_t chunk_frames = 0;
   int64_t last_coarse_tiles = -1;     // tiles the last coarse-to-fine max(P) evaluated in full (diagnostics)
   int pipe_mode = FMCW_PIPE_AUTO;
@@ -2179,6 +2183,195 @@ int fmcw_cfar(fmcw_ctx* c, const fmcw_cfar_params* q, const void* rd, int32_t rd
     return cfar_host_one(d, q, static_cast<const char*>(rd) + (size_t)f0 * fin, rd_dtype, n, nr, nd, count + f0,
                          ridx + f0 * K, didx + f0 * K, power + f0 * K, noise + f0 * K,
                          mask ? mask + (size_t)f0 * nr * nd : nullptr);
+  });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Doppler-time and range-time signatures of the RD map (kernels_sig.hip)
+// ---------------------------------------------------------------------------
+static int sig_check_impl(const fmcw_sig_params* q, int32_t nr, int32_t nd) {
+  if (!q) return fail(FMCW_E_ARG, "sig params is NULL");
+  if (nr < 16 || nr > 2048 || (nr & (nr - 1))) return fail(FMCW_E_ARG, "sig: nr must be a power of two in [16, 2048]");
+  if (nd < 4 || nd > 1024 || (nd & (nd - 1))) return fail(FMCW_E_ARG, "sig: nd must be a power of two in [4, 1024]");
+  if (q->r_lo > q->r_hi) return fail(FMCW_E_ARG, "sig: r_lo > r_hi");
+  if (!(q->r_lo == 0 && q->r_hi == 0) && (q->r_lo < 1 || q->r_hi > nr))
+    return fail(FMCW_E_ARG, "sig: the gate r_lo..r_hi must lie in 1..nr (or be 0, 0 for all rows)");
+  if (q->track_half < 0 || q->track_half > 64) return fail(FMCW_E_ARG, "sig: track_half must be in [0, 64]");
+  if (q->dc_half < -1) return fail(FMCW_E_ARG, "sig: dc_half must be >= -1 (-1 leaves no Doppler bin out)");
+  if (2 * (int64_t)q->dc_half + 1 >= nd) return fail(FMCW_E_ARG, "sig: 2 dc_half + 1 must be < nd");
+  if (q->flags & ~FMCW_SIG_DB) return fail(FMCW_E_ARG, "sig: unknown flag bits");
+  if (!(q->floor_db < 0.f) || !std::isfinite(q->floor_db)) return fail(FMCW_E_ARG, "sig: floor_db must be finite and < 0");
+  return FMCW_OK;
+}
+
+// One shard of fmcw_sig: both maps and both maxima of frames [0, F) into the context's sg_out
+// ([F][nd], [F][nr], 2 floats), chunk by chunk.  The maps stay there for sig_host_finish.
+namespace {
+struct SigOut {
+  size_t o_dt, o_rt, o_max, bytes;
+  SigOut(int64_t F, int nr, int nd) {
+    Arena ar;
+    o_dt = ar.add((size_t)F * nd * 4);
+    o_rt = ar.add((size_t)F * nr * 4);
+    o_max = ar.add(8);
+    bytes = ar.off;
+  }
+};
+}  // namespace
+
+static int sig_host_one(fmcw_ctx* c, const fmcw_sig_params* q, const char* rd, int32_t dtype, int64_t F, int32_t nr,
+                        int32_t nd, const int32_t* center, int32_t cstride, float* mx) {
+  CHK(set_device(c));
+  hipStream_t s = c->stream;
+  const size_t fin = (size_t)nr * nd * esize(dtype);
+  const int64_t Fc = host_chunk(fin, F);
+  const SigOut so(F, nr, nd);
+  CHK(c->sg_out.ensure(so.bytes));
+  CHK(c->sg_in.ensure((size_t)Fc * fin));
+  char* const o = c->sg_out.as<char>();
+  HIPCHK(hipMemsetAsync(o + so.o_max, 0, 8, s));
+  if (center) {
+    CHK(c->sg_ctr.ensure((size_t)F * cstride * 4));
+    HIPCHK(hipMemcpyAsync(c->sg_ctr.p, center, (size_t)F * cstride * 4, hipMemcpyHostToDevice, s));
+  }
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    const int64_t nf = std::min(Fc, F - f0);
+    HIPCHK(hipMemcpyAsync(c->sg_in.p, rd + (size_t)f0 * fin, (size_t)nf * fin, hipMemcpyHostToDevice, s));
+    CHK(fmcw_sig_device(c, q, c->sg_in.p, dtype, nf, nr, nd, center ? c->sg_ctr.as<int32_t>() + f0 * cstride : nullptr,
+                        cstride, reinterpret_cast<float*>(o + so.o_dt) + f0 * nd,
+                        reinterpret_cast<float*>(o + so.o_rt) + f0 * nr, reinterpret_cast<float*>(o + so.o_max),
+                        reinterpret_cast<float*>(o + so.o_max) + 1, s));
+    HIPCHK(hipStreamSynchronize(s));           // the chunk buffer is reused by the next chunk
+  }
+  HIPCHK(hipMemcpyAsync(mx, o + so.o_max, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return FMCW_OK;
+}
+
+// The shard's maps to the host, in dB relative to the global maxima gmx when db.
+static int sig_host_finish(fmcw_ctx* c, int64_t F, int32_t nr, int32_t nd, bool db, const float* gmx, float floor_db,
+                           float* dt, float* rt) {
+  CHK(set_device(c));
+  hipStream_t s = c->stream;
+  const SigOut so(F, nr, nd);
+  char* const o = c->sg_out.as<char>();
+  float* const d_dt = reinterpret_cast<float*>(o + so.o_dt);
+  float* const d_rt = reinterpret_cast<float*>(o + so.o_rt);
+  float* const d_mx = reinterpret_cast<float*>(o + so.o_max);
+  if (db) {
+    HIPCHK(hipMemcpyAsync(d_mx, gmx, 8, hipMemcpyHostToDevice, s));
+    if (dt) CHK(fmcw_sig_db_device(c, d_dt, F * nd, d_mx, floor_db, d_dt, s));
+    if (rt) CHK(fmcw_sig_db_device(c, d_rt, F * nr, d_mx + 1, floor_db, d_rt, s));
+  }
+  if (dt) HIPCHK(hipMemcpyAsync(dt, d_dt, (size_t)F * nd * 4, hipMemcpyDeviceToHost, s));
+  if (rt) HIPCHK(hipMemcpyAsync(rt, d_rt, (size_t)F * nr * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return FMCW_OK;
+}
+
+extern "C" {
+
+int fmcw_sig_check(const fmcw_sig_params* q, int32_t nr, int32_t nd) { return sig_check_impl(q, nr, nd); }
+
+int fmcw_sig_device(fmcw_ctx* c, const fmcw_sig_params* q, const void* d_rd, int32_t rd_dtype, int64_t F, int32_t nr,
+                    int32_t nd, const int32_t* d_center, int32_t center_stride, float* d_doppler_time,
+                    float* d_range_time, float* d_dt_max, float* d_rt_max, void* stream) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(sig_check_impl(q, nr, nd));
+  if (rd_dtype != FMCW_C64 && rd_dtype != FMCW_C32H) return fail(FMCW_E_ARG, "bad rd_dtype");
+  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
+  if (!d_doppler_time && !d_range_time) return fail(FMCW_E_ARG, "sig: both maps are NULL");
+  if (d_center && center_stride < 1) return fail(FMCW_E_ARG, "sig: center_stride must be >= 1");
+  if (F == 0) return FMCW_OK;
+  if (!d_rd) return fail(FMCW_E_ARG, "required pointer is NULL");
+  if (reinterpret_cast<uintptr_t>(d_rd) & 15) return fail(FMCW_E_ARG, "sig: d_rd must be 16-byte aligned");
+  CHK(set_device(c));
+  hipStream_t s = pick(c, stream);
+  fmcw::SigArgs a{};
+  a.h = rd_dtype == FMCW_C32H;
+  a.scale2 = a.h ? ((float)nr * (float)nd) * ((float)nr * (float)nd) : 1.f;
+  a.NR = nr; a.ND = nd;
+  a.g0 = q->r_lo == 0 ? 0 : q->r_lo - 1;
+  a.g1 = q->r_hi == 0 ? nr - 1 : q->r_hi - 1;
+  a.th = q->track_half;
+  a.dc = q->dc_half;
+  a.center = d_center;
+  a.cstride = d_center ? center_stride : 0;
+  a.dt = d_doppler_time; a.rt = d_range_time;
+  a.dt_max = d_doppler_time ? d_dt_max : nullptr;
+  a.rt_max = d_range_time ? d_rt_max : nullptr;
+  fmcw::sig_plan(a);
+  // frames per launch: at most 256 MiB of column-sum scratch (the results do not depend on the cut)
+  const size_t per = fmcw::sig_scratch_per_frame(a);
+  const int64_t Fc = std::max<int64_t>(1, std::min<int64_t>({F, per ? (int64_t)(((size_t)256 << 20) / per) : F,
+                                                             (int64_t)0x7fffffff / 256}));
+  if (per) {
+    int st = FMCW_OK;
+    a.part = static_cast<float*>(c->sig_scr.get(s, (size_t)Fc * per, &st));
+    CHK(st);
+  }
+  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    a.F = std::min(Fc, F - f0);
+    a.rd = static_cast<const char*>(d_rd) + (size_t)f0 * fin;
+    a.center = d_center ? d_center + f0 * center_stride : nullptr;
+    a.dt = d_doppler_time ? d_doppler_time + f0 * nd : nullptr;
+    a.rt = d_range_time ? d_range_time + f0 * nr : nullptr;
+    HIPCHK(fmcw::launch_sig(a, s));
+  }
+  if (per) CHK(c->sig_scr.done(s));
+  return FMCW_OK;
+}
+
+int fmcw_sig_db_device(fmcw_ctx* c, const float* d_map, int64_t n, const float* d_max, float floor_db, float* d_out,
+                       void* stream) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  if (n < 0) return fail(FMCW_E_ARG, "n < 0");
+  if (!(floor_db < 0.f) || !std::isfinite(floor_db)) return fail(FMCW_E_ARG, "sig: floor_db must be finite and < 0");
+  if (n == 0) return FMCW_OK;
+  if (!d_map || !d_max || !d_out) return fail(FMCW_E_ARG, "required pointer is NULL");
+  CHK(set_device(c));
+  HIPCHK(fmcw::launch_sig_db(d_map, n, d_max, floor_db, d_out, pick(c, stream)));
+  return FMCW_OK;
+}
+
+int fmcw_sig(fmcw_ctx* c, const fmcw_sig_params* q, const void* rd, int32_t rd_dtype, int64_t F, int32_t nr, int32_t nd,
+             const int32_t* center, int32_t center_stride, float* doppler_time, float* range_time, float* dt_max,
+             float* rt_max) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(sig_check_impl(q, nr, nd));
+  if (rd_dtype != FMCW_C64 && rd_dtype != FMCW_C32H) return fail(FMCW_E_ARG, "bad rd_dtype");
+  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
+  if (!doppler_time && !range_time) return fail(FMCW_E_ARG, "sig: both maps are NULL");
+  if (center && center_stride < 1) return fail(FMCW_E_ARG, "sig: center_stride must be >= 1");
+  if (F == 0) {
+    if (dt_max) *dt_max = 0.f;
+    if (rt_max) *rt_max = 0.f;
+    return FMCW_OK;
+  }
+  if (!rd) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
+  const int world = 1 + (int)c->peers.size();
+  std::vector<float> mx(2 * (size_t)world, 0.f);
+  // frames are independent: contiguous shards; every shard forms both maps on its device
+  CHK(over_devices(c, F, [&](fmcw_ctx* d, int g, int64_t f0, int64_t n) {
+    return sig_host_one(d, q, static_cast<const char*>(rd) + (size_t)f0 * fin, rd_dtype, n, nr, nd,
+                        center ? center + f0 * center_stride : nullptr, center_stride, &mx[2 * (size_t)g]);
+  }));
+  float gmx[2] = {0.f, 0.f};                   // a maximum of non-negative floats does not depend on order
+  for (int g = 0; g < world; ++g) {
+    gmx[0] = std::max(gmx[0], mx[2 * (size_t)g]);
+    gmx[1] = std::max(gmx[1], mx[2 * (size_t)g + 1]);
+  }
+  if (dt_max) *dt_max = gmx[0];
+  if (rt_max) *rt_max = gmx[1];
+  // second pass, after the maxima are combined (:282-283): dB relative to the global maximum, then home
+  const bool db = (q->flags & FMCW_SIG_DB) != 0;
+  return over_devices(c, F, [&](fmcw_ctx* d, int, int64_t f0, int64_t n) {
+    return sig_host_finish(d, n, nr, nd, db, gmx, q->floor_db, doppler_time ? doppler_time + f0 * nd : nullptr,
+                           range_time ? range_time + f0 * nr : nullptr);
   });
 }
 

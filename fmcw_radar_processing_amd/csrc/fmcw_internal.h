@@ -320,6 +320,30 @@ void cfar_plan(CfarArgs& a, int64_t F);
 size_t cfar_scratch_per_frame(const CfarArgs& a);
 hipError_t launch_cfar(const CfarArgs& a, hipStream_t s);
 
+// Doppler-time / range-time signatures of the RD map (kernels_sig.hip): k_sig + k_sig_gather, k_sig_db
+struct SigArgs {
+  const void* rd;          // [F][NR][ND] c64, or c32h (h) holding D / (NR ND); 16-byte aligned
+  int h;
+  float scale2;            // (NR * ND)^2 when h, else 1: the sums come out in the units of |D|^2
+  int64_t F;
+  int NR, ND;
+  int g0, g1;              // gated rows, 0-based, inclusive
+  int th;                  // track_half (used with center)
+  int dc;                  // dc_half, -1 = keep every Doppler bin
+  const int32_t* center;   // [F * cstride] 1-based row of the frame's window centre, or nullptr: the gate
+  int64_t cstride;
+  int SR, slabs;           // rows per slab, slabs per frame                 (sig_plan)
+  float* part;             // scratch [F][slabs][ND] column sums, when slabs > 1 and dt
+  float* dt;               // [F][ND] or nullptr
+  float* rt;               // [F][NR] or nullptr
+  float* dt_max;           // running maxima or nullptr
+  float* rt_max;
+};
+void sig_plan(SigArgs& a);
+size_t sig_scratch_per_frame(const SigArgs& a);
+hipError_t launch_sig(const SigArgs& a, hipStream_t s);
+hipError_t launch_sig_db(const float* map, int64_t n, const float* mx, float floor_db, float* out, hipStream_t s);
+
 bool range_size_supported(int nr);
 bool doppler_size_supported(int nd);
 

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import FMCW_C32H, FMCW_C64, STAGES, FmcwError, check
-from .params import CfarConfig, FmcwConfig
+from .params import CfarConfig, FmcwConfig, SigConfig
 
 
 def _ptr(a) -> ct.c_void_p:
@@ -296,6 +296,75 @@ class Engine:
         self.process_device(d_iq, F, in_dtype, outs, d_cube=d_cube, d_rd=d_rd, out_dtype=out_dtype,
                             probe_column=probe_column, stream=stream)
         self.cfar_device(q, d_rd, out_dtype, F, cfg.nr, cfg.nd, cfar_outs, d_mask=d_mask, stream=stream)
+
+    # ---- Doppler-time / range-time signatures of the RD map (include/fmcw.h, fmcw_sig_params) ----
+    def signature(self, rd: np.ndarray, q: SigConfig, center: np.ndarray | None = None) -> dict:
+        """Signatures of rd: complex64 [F][nr][nd], or float16 [F][nr][nd][2] holding D / (nr nd).
+        Host arrays, sharded over the context's devices.  center: None (the rows are the gate), int32
+        [F] or [F][stride] whose first column is the 1-based centre row of each frame (0: no target).
+        Returns doppler_time [F][nd], range_time [F][nr] (in dB with q.db), the global maxima dt_max,
+        rt_max of the linear maps and, once set_taps has given the geometry, the axes speed_mps [nd]
+        and range_m [nr]."""
+        if rd.dtype == np.complex64 and rd.ndim == 3:
+            rd, dt = np.ascontiguousarray(rd), FMCW_C64
+        elif rd.dtype == np.float16 and rd.ndim == 4 and rd.shape[-1] == 2:
+            rd, dt = np.ascontiguousarray(rd), FMCW_C32H
+        else:
+            raise TypeError("rd must be complex64 [F][nr][nd] or float16 [F][nr][nd][2]")
+        F, nr, nd = rd.shape[:3]
+        stride = 0
+        if center is not None:
+            center = np.ascontiguousarray(center, np.int32)
+            if center.ndim not in (1, 2) or center.shape[0] != F:
+                raise ValueError("center must be int32 [F] or [F][stride]")
+            stride = 1 if center.ndim == 1 else center.shape[1]
+        out = dict(doppler_time=np.zeros((F, nd), np.float32), range_time=np.zeros((F, nr), np.float32))
+        dmx, rmx = ct.c_float(0.0), ct.c_float(0.0)
+        qa = q.abi()
+        check(self.lib.fmcw_sig(self.h, ct.byref(qa), _ptr(rd), dt, F, nr, nd, _ptr(center), stride,
+                                _ptr(out["doppler_time"]), _ptr(out["range_time"]), ct.byref(dmx), ct.byref(rmx)))
+        out["dt_max"], out["rt_max"] = np.float32(dmx.value), np.float32(rmx.value)
+        if self.cfg is not None and (self.cfg.nr, self.cfg.nd) == (nr, nd):
+            out["speed_mps"] = self.cfg.speed(np.arange(1, nd + 1))
+            out["range_m"] = self.cfg.range_m(np.arange(1, nr + 1))
+        return out
+
+    def signature_device(self, q: SigConfig, d_rd, rd_dtype: int, F: int, nr: int, nd: int, d_doppler_time=None,
+                         d_range_time=None, d_dt_max=None, d_rt_max=None, d_center=None, center_stride: int = 1,
+                         stream=None) -> None:
+        """fmcw_sig_device: d_rd [F][nr][nd] of rd_dtype on the device; d_doppler_time [F][nd] and
+        d_range_time [F][nr] float32 (either may be None); d_dt_max / d_rt_max one float32 each,
+        zeroed by the caller; d_center int32 with center_stride entries per frame, or None for the
+        fixed gate.  Asynchronous on `stream`."""
+        qa = q.abi()
+        with _sided(stream) as hs:
+            check(self.lib.fmcw_sig_device(self.h, ct.byref(qa), _ptr(d_rd), int(rd_dtype), int(F), int(nr), int(nd),
+                                           _ptr(d_center), int(center_stride), _ptr(d_doppler_time),
+                                           _ptr(d_range_time), _ptr(d_dt_max), _ptr(d_rt_max), hs))
+
+    def signature_db_device(self, d_map, n: int, d_max, floor_db: float, d_out, stream=None) -> None:
+        """fmcw_sig_db_device: d_out[i] = max(10 log10(d_map[i] / *d_max), floor_db); d_out may be d_map."""
+        with _sided(stream) as hs:
+            check(self.lib.fmcw_sig_db_device(self.h, _ptr(d_map), int(n), _ptr(d_max), float(floor_db), _ptr(d_out),
+                                              hs))
+
+    def process_signature_device(self, d_iq, F: int, in_dtype: int, outs: dict, q: SigConfig, d_rd, sig_outs: dict,
+                                 out_dtype: int = FMCW_C64, track: bool = True, d_cube=None, probe_column: int = 0,
+                                 stream=None) -> None:
+        """IQ in, signatures out, on one stream with no host round trip: process_device writing the
+        RD map to d_rd (out_dtype), then signature_device over it.  With `track` the centre of each
+        frame is its strongest target, outs["tgt_range_idx"] at stride max_targets (q.track_half bins
+        either side); without, the rows are q's gate.  sig_outs holds doppler_time, range_time,
+        dt_max, rt_max (device buffers, any of them may be missing or None, not both maps)."""
+        cfg = self._need()
+        if d_rd is None:
+            raise ValueError("process_signature_device needs an RD buffer")
+        self.process_device(d_iq, F, in_dtype, outs, d_cube=d_cube, d_rd=d_rd, out_dtype=out_dtype,
+                            probe_column=probe_column, stream=stream)
+        self.signature_device(q, d_rd, out_dtype, F, cfg.nr, cfg.nd, sig_outs.get("doppler_time"),
+                              sig_outs.get("range_time"), sig_outs.get("dt_max"), sig_outs.get("rt_max"),
+                              d_center=outs["tgt_range_idx"] if track else None, center_stride=cfg.max_targets,
+                              stream=stream)
 
     # ---- timing -----------------------------------------------------------------
     def timing(self, level: int) -> None:

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import windows
-from ._lib import FMCW_CFAR_LOCAL_MAX, CfarParams, Params
+from ._lib import FMCW_CFAR_LOCAL_MAX, FMCW_SIG_DB, CfarParams, Params, SigParams
 
 C0 = 3e8  # radar_processing.m:67
 
@@ -162,6 +162,53 @@ class CfarConfig:
         q.r_lo, q.r_hi = int(sel[0]), int(sel[-1])
         q.alpha = cls.alpha_for(q.n_train_full, pfa)
         return q
+
+
+@dataclass
+class SigConfig:
+    """fmcw_sig_params (include/fmcw.h): Doppler-time and range-time signatures of the RD map.  The
+    gate r_lo..r_hi is 1-based and inclusive, (0, 0) = every row; track_half is used only with a
+    centre array (rows centre - h .. centre + h, clipped to the gate); dc_half leaves the Doppler bins
+    |d - nd/2| <= dc_half out of the range-time map (-1: none); db (host call only) returns both maps
+    in dB relative to their global maximum, clamped at floor_db."""
+    r_lo: int = 0
+    r_hi: int = 0
+    track_half: int = 0
+    dc_half: int = -1
+    db: bool = False
+    floor_db: float = -80.0
+
+    def abi(self) -> SigParams:
+        return SigParams(self.r_lo, self.r_hi, self.track_half, self.dc_half, FMCW_SIG_DB if self.db else 0,
+                         self.floor_db)
+
+    def validate(self, nr: int, nd: int) -> None:
+        """The rules of fmcw_sig_check; ValueError naming the first one violated."""
+        if nr < 16 or nr > 2048 or nr & (nr - 1):
+            raise ValueError("sig: nr must be a power of two in [16, 2048]")
+        if nd < 4 or nd > 1024 or nd & (nd - 1):
+            raise ValueError("sig: nd must be a power of two in [4, 1024]")
+        if self.r_lo > self.r_hi:
+            raise ValueError("sig: r_lo > r_hi")
+        if (self.r_lo, self.r_hi) != (0, 0) and (self.r_lo < 1 or self.r_hi > nr):
+            raise ValueError("sig: the gate r_lo..r_hi must lie in 1..nr (or be 0, 0 for all rows)")
+        if not 0 <= self.track_half <= 64:
+            raise ValueError("sig: track_half must be in [0, 64]")
+        if self.dc_half < -1:
+            raise ValueError("sig: dc_half must be >= -1")
+        if 2 * self.dc_half + 1 >= nd:
+            raise ValueError("sig: 2 dc_half + 1 must be < nd")
+        if not (self.floor_db < 0 and np.isfinite(self.floor_db)):
+            raise ValueError("sig: floor_db must be finite and < 0")
+
+    @classmethod
+    def for_config(cls, cfg: "FmcwConfig", track_half: int = 2, dc_half: int = 0, db: bool = False,
+                   floor_db: float = -80.0) -> "SigConfig":
+        """The signatures over the peak rule's gate (CfarConfig.for_config), following the strongest
+        target with track_half bins either side when a centre array is given."""
+        g = CfarConfig.for_config(cfg)
+        return cls(r_lo=g.r_lo, r_hi=g.r_hi, track_half=int(track_half), dc_half=int(dc_half), db=bool(db),
+                   floor_db=float(floor_db))
 
 
 def derive_params(device: dict, nr: int = 256, nd: int = 16, mode: str = PARITY, **over) -> FmcwConfig:

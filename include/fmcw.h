@@ -41,7 +41,9 @@ extern "C" {
 /* 3: FMCW_PIPE_ONEPASS names the XCD-team schedule (E_ARG where the XCD census fails),
  *    fmcw_default_devices, FMCW_JSON_BOOL
  * 4: + the CFAR entry points (fmcw_cfar_check, fmcw_cfar_alpha, fmcw_cfar_device, fmcw_cfar)
- *    and timing stage 10, added within ABI 4: nothing that existed changed */
+ *    and timing stage 10, added within ABI 4: nothing that existed changed
+ *    + the signature entry points (fmcw_sig_check, fmcw_sig_device, fmcw_sig_db_device,
+ *    fmcw_sig), added within ABI 4 in the same way */
 #define FMCW_ABI_VERSION 4
 
 typedef enum fmcw_status {
@@ -370,6 +372,72 @@ int fmcw_cfar_device(fmcw_ctx* ctx, const fmcw_cfar_params* q, const void* d_rd,
 int fmcw_cfar(fmcw_ctx* ctx, const fmcw_cfar_params* q, const void* rd, int32_t rd_dtype, int64_t F,
               int32_t nr, int32_t nd, int32_t* det_count, int32_t* det_range_idx,
               int32_t* det_doppler_idx, float* det_power, float* det_noise, uint8_t* mask);
+
+/* ---------------------------------------------------------------------------
+ * Doppler-time (micro-Doppler) and range-time signatures of the RD map (added within ABI 4;
+ * beyond the reference, whose spectrogram of abs(slow_time) at one range bin, :258-270, loses
+ * the sign of the velocity and joins chirps of different frames).  Indices below are 0-based;
+ * every index argument is 1-based.
+ *   rd [F][nr][nd]   as for fmcw_cfar_device (same dtypes, size limits and 16-byte alignment).
+ *                    P[r][d] = re^2 + im^2 of the stored value; fp16 storage: times (nr*nd)^2
+ *                    (exact), so the outputs are in the units of |range_Doppler_tx1rx1|^2.
+ *   Rows of frame f: without a centre array, the gate r_lo..r_hi.  With one,
+ *     c = d_center[f * center_stride] is a 1-based row (0: the frame has no target):
+ *     the rows c-1-track_half .. c-1+track_half intersected with the gate; c = 0, an empty
+ *     intersection or a c outside 0..nr (never read through): no rows.  d_tgt_range_idx of
+ *     fmcw_process* with center_stride = max_targets follows the strongest target (:258).
+ *   doppler_time [F][nd]   sum of P[r][d] over the frame's rows
+ *   range_time   [F][nr]   sum of P[r][d] over the Doppler bins d that are not left out
+ *                          (circular |d - nd/2| <= dc_half is left out: zero Doppler sits at
+ *                          bin nd/2 after the fftshift of :219), for the frame's rows; 0 for
+ *                          every other row.  A frame with no rows gives zeros in both.
+ *   Either map may be NULL, not both.
+ *   Every output is a sum of non-negative terms by additions only (no guard band is
+ *   subtracted from a full sum): within (N + 8) 2^-24 relative of the exact sum of the
+ *   stored values, N the number of cells summed.  Results are bit-identical from call to
+ *   call and do not depend on F or on how a host call is sharded or chunked.
+ *   d_dt_max / d_rt_max (device floats or NULL): running maxima of everything written to
+ *   the corresponding map, raised atomically; the caller zeroes them first.
+ *   Constraints: 1 <= r_lo <= r_hi <= nr or r_lo = r_hi = 0 (all rows); track_half in
+ *     0..64; dc_half >= -1 (-1 leaves no bin out) and 2 dc_half + 1 < nd; floor_db finite
+ *     and < 0; no unknown flag bits.
+ *   Measured on one MI355X over 4096 frames of 1024 x 256, every row, both maps
+ *   (profiles/sig_bench.json, 2026-10-19): 1.50 ms for FMCW_C64 and 0.77 ms for FMCW_C32H,
+ *   beside 2.63 / 1.32 ms for fmcw_copy_device on the same RD bytes in the same run
+ *   (DESIGN.md 4.5).
+ * ------------------------------------------------------------------------- */
+enum { FMCW_SIG_DB = 1 };           /* host call only: outputs in dB, see fmcw_sig */
+typedef struct fmcw_sig_params {
+  int32_t r_lo, r_hi;      /* 1-based inclusive range gate, 0/0 = all rows */
+  int32_t track_half;      /* used only with a centre array; 0..64 */
+  int32_t dc_half;         /* range-time map: Doppler bins left out around nd/2; -1 = none */
+  int32_t flags;           /* FMCW_SIG_DB */
+  float   floor_db;        /* < 0, finite; lower clamp of the dB outputs */
+} fmcw_sig_params;
+
+/* Host only, no context: FMCW_E_ARG (with a message) for any violation of the constraints. */
+int fmcw_sig_check(const fmcw_sig_params* q, int32_t nr, int32_t nd);
+
+/* Device pointers (d_rd 16-byte aligned), asynchronous on `stream`; needs no fmcw_set_taps.
+ * Acts on the context's first device.  FMCW_SIG_DB is ignored here.  F = 0 is a no-op. */
+int fmcw_sig_device(fmcw_ctx* ctx, const fmcw_sig_params* q, const void* d_rd, int32_t rd_dtype,
+                    int64_t F, int32_t nr, int32_t nd, const int32_t* d_center, int32_t center_stride,
+                    float* d_doppler_time, float* d_range_time, float* d_dt_max, float* d_rt_max,
+                    void* stream);
+
+/* out[i] = max(10 log10(map[i] / *d_max), floor_db) with log10f; floor_db where map[i] == 0
+ * or *d_max == 0.  d_out may alias d_map. */
+int fmcw_sig_db_device(fmcw_ctx* ctx, const float* d_map, int64_t n, const float* d_max, float floor_db,
+                       float* d_out, void* stream);
+
+/* Host pointers: staged, sharded over the context's devices and chunked as fmcw_cfar is
+ * (bit-identical).  center: a host array or NULL.  *dt_max / *rt_max (may be NULL) always
+ * receive the global maxima of the two linear maps.  With FMCW_SIG_DB both maps come back in
+ * dB relative to their global maximum (a second pass after the maxima are combined, the order
+ * of :282-283), clamped at floor_db. */
+int fmcw_sig(fmcw_ctx* ctx, const fmcw_sig_params* q, const void* rd, int32_t rd_dtype, int64_t F,
+             int32_t nr, int32_t nd, const int32_t* center, int32_t center_stride, float* doppler_time,
+             float* range_time, float* dt_max, float* rt_max);
 
 /* ---------------------------------------------------------------------------
  * spectrogram.png, replacing radar_processing.m:331-348:

@@ -27,6 +27,13 @@
  *                                        fmcw_cfar_params; rd: single complex Nd x Nr x F (the C array
  *                                        [F][Nr][Nd]: permute(range_Doppler, [2 1 3])); ridx ... noise are
  *                                        max_det x F
+ *   [dt, rt, dt_max, rt_max] = fmcw_mex('signature', Q, rd[, center])  -> fmcw_sig: Doppler-time (micro-Doppler)
+ *                                        and range-time signatures of an RD map (beyond the reference); Q: a
+ *                                        struct with the fields of fmcw_sig_params; rd as for 'cfar'; center:
+ *                                        int32, one 1-based range row per frame (0: no target), e.g.
+ *                                        ridx(1, :) of 'process', or absent / empty for the fixed gate; dt is
+ *                                        Nd x F, rt Nr x F (in dB when Q.flags has FMCW_SIG_DB), the maxima
+ *                                        are those of the linear maps
  *   fmcw_mex('close')                                             -> fmcw_ctx_destroy
  *
  * P is a struct with the fields of fmcw_params (nts, pn, nr, nd, max_targets,
@@ -258,6 +265,39 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     plhs[4] = mxCreateNumericMatrix(K, F, mxSINGLE_CLASS, mxREAL);   /* noise estimate S / N */
     check(fmcw_cfar(g_ctx, &q, mxGetComplexSingles(rd), FMCW_C64, F, nr, nd, mxGetInt32s(plhs[0]), mxGetInt32s(plhs[1]),
                     mxGetInt32s(plhs[2]), mxGetSingles(plhs[3]), mxGetSingles(plhs[4]), NULL));
+    return;
+  }
+  if (!strcmp(cmd, "signature")) {          /* [dt, rt, dt_max, rt_max] = fmcw_mex('signature', Q, rd[, center]) */
+    if (nrhs != 3 && nrhs != 4) mexErrMsgIdAndTxt("fmcw:arg", "signature: Q, rd[, center]");
+    const mxArray* s = prhs[1];
+    const mxArray* rd = prhs[2];
+    if (!mxIsStruct(s)) mexErrMsgIdAndTxt("fmcw:arg", "Q must be a struct");
+    fmcw_sig_params q;
+    q.r_lo = (int32_t)field(s, "r_lo");
+    q.r_hi = (int32_t)field(s, "r_hi");
+    q.track_half = (int32_t)field(s, "track_half");
+    q.dc_half = (int32_t)field(s, "dc_half");
+    q.flags = (int32_t)field(s, "flags");
+    q.floor_db = (float)field(s, "floor_db");
+    if (!mxIsSingle(rd) || !mxIsComplex(rd) || mxGetNumberOfDimensions(rd) < 2)
+      mexErrMsgIdAndTxt("fmcw:arg", "rd must be single complex Nd x Nr x F");
+    const mwSize* dims = mxGetDimensions(rd);
+    const int64_t F = mxGetNumberOfDimensions(rd) >= 3 ? (int64_t)dims[2] : 1;
+    const int32_t nd = (int32_t)dims[0], nr = (int32_t)dims[1];
+    check(fmcw_sig_check(&q, nr, nd));
+    const int32_t* center = NULL;
+    if (nrhs == 4 && mxGetNumberOfElements(prhs[3]) > 0) {
+      if (!mxIsInt32(prhs[3]) || (int64_t)mxGetNumberOfElements(prhs[3]) != F)
+        mexErrMsgIdAndTxt("fmcw:arg", "center must be int32 with one entry per frame");
+      center = mxGetInt32s(prhs[3]);
+    }
+    float dmx = 0.f, rmx = 0.f;
+    plhs[0] = mxCreateNumericMatrix((mwSize)nd, (mwSize)F, mxSINGLE_CLASS, mxREAL);   /* Doppler-time map */
+    plhs[1] = mxCreateNumericMatrix((mwSize)nr, (mwSize)F, mxSINGLE_CLASS, mxREAL);   /* range-time map */
+    check(fmcw_sig(g_ctx, &q, mxGetComplexSingles(rd), FMCW_C64, F, nr, nd, center, 1, mxGetSingles(plhs[0]),
+                   mxGetSingles(plhs[1]), &dmx, &rmx));
+    plhs[2] = mxCreateDoubleScalar((double)dmx);
+    plhs[3] = mxCreateDoubleScalar((double)rmx);
     return;
   }
   mexErrMsgIdAndTxt("fmcw:arg", "unknown command '%s'", cmd);
