@@ -320,6 +320,8 @@ def psd_db(P: np.ndarray) -> np.ndarray:
 def log_freq_bins(fs: float, nfft: int, nbins: int = 1024) -> np.ndarray:
     """:293-296; MIN_FREQ = min(F(F>0)) = fs/nfft, MAX_FREQ = fs/2."""
     Fv = np.arange(nfft // 2 + 1) * fs / nfft
+    if nbins == 1:                                 # MATLAB's logspace(a, b, 1) is 10^b (numpy's: 10^a)
+        return np.array([Fv.max()])
     return np.logspace(np.log10(Fv[Fv > 0].min()), np.log10(Fv.max()), nbins)
 
 

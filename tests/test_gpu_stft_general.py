@@ -1,0 +1,416 @@
+"""The general STFT kernel (k_stft_power: any window of 1..256 taps, any hop, any even nfft >= wlen)
+and the dB / log-frequency stage behind it, against the float64 direct-DFT reference of
+tests/stft_reference.py.
+
+Every other STFT test uses a 20-tap window at hop 1..4, which is the 20-tap fast path; here the window
+is never 20 taps at hop <= 4, so fmcw_stft_power_device and fmcw_stft take their general branch.  The
+window is asymmetric (a reversed tap index passes every symmetric one), the shapes are the ones at which
+the kernel's staging, tiling and Horner recurrence change behaviour, and an impulse gives a known answer.
+
+The bar is TOL_FP32_DB: |dB error| <= 1e-3 where the float64 psd is >= -80 dB; below the
+floor an output only has to stay below it.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+from oracle import oracle as O
+from tests import stft_reference as R
+from tests.helpers import TOL_FP32_DB
+
+pytestmark = pytest.mark.gpu
+
+FS = 1250.0
+FLOOR = -80.0
+
+# (wlen, noverlap, nfft, L)
+PARITY = [(1, 0, 2, 50),            # one tap: the Horner loop runs zero times; both bins unscaled
+          (2, 1, 2, 40),
+          (5, 3, 6, 60),
+          (19, 18, 64, 300), (21, 20, 64, 300),      # the neighbours of the 20-tap dispatch
+          (20, 15, 64, 400),        # hop 5: the first hop off the fast path at 20 taps
+          (32, 0, 32, 16000),       # nfft = wlen, 500 segments in tiles of 240: three workgroups, the last partial
+          (64, 0, 100, 1000),
+          (128, 121, 300, 1200),
+          (256, 255, 256, 700), (256, 0, 300, 3000), (256, 128, 1000, 2000),   # the largest window
+          (24, 12, 16384, 150)]     # more than 4096 bins: one segment per workgroup
+KAISER = (64, 48, 100, 600)
+
+
+def _window(shape):
+    wlen = shape[0]
+    if shape == KAISER:
+        return O.stft_window("kaiser", wlen).astype(np.float32)
+    return R.asym_window(wlen, wlen)
+
+
+@functools.lru_cache(maxsize=None)
+def _ref(shape):
+    """(x float32, w float32, P float64 [nseg][nb], its dB map), computed once per shape and shared."""
+    wlen, noverlap, nfft, L = shape
+    x = R.magnitude_signal(L, L + wlen)
+    w = _window(shape)
+    P = R.stft_power(x, w, noverlap, nfft, FS)
+    db = R.psd_db(P)
+    for a in (x, w, P, db):
+        a.setflags(write=False)
+    return x, w, P, db
+
+
+def _power(engine, x, w, noverlap, nfft, *, L=None, max_seg=None, store=True, slow=None, flist=None, pn=None, halo=None,
+           halo_len=None, pmax=None, pad=3):
+    """One fmcw_stft_power_device call.  d_P is NaN-filled and `pad` rows longer than the larger of
+    max_seg and the true segment count, so a write past either shows."""
+    import torch
+    dev = "cuda"
+    x = np.ascontiguousarray(x, np.float32)
+    L = len(x) if L is None else L
+    if slow is None:
+        slow, flist, pn = x.reshape(1, -1), [0], len(x)
+    wlen = len(w)
+    H = 0 if halo is None else (len(halo) if halo_len is None else halo_len)
+    true_n = R.nseg_of(L + H, wlen, noverlap)
+    max_seg = true_n + pad if max_seg is None else max_seg
+    nb = nfft // 2 + 1
+    t = dict(slow=torch.from_numpy(np.array(slow, np.float32)).to(dev),      # copies: the shared inputs are read-only
+             flist=torch.tensor(flist, dtype=torch.int32, device=dev),
+             len=torch.tensor([L], dtype=torch.int64, device=dev),
+             win=torch.from_numpy(np.array(w, np.float32)).to(dev),
+             P=torch.full((max(max_seg, true_n) + pad, nb), np.nan, dtype=torch.float32, device=dev),
+             pmax=torch.zeros(1, dtype=torch.float32, device=dev) if pmax is None else pmax,
+             nseg=torch.full((1,), -1, dtype=torch.int64, device=dev))
+    d_halo = d_hl = None
+    if halo is not None:
+        d_halo = torch.from_numpy(np.ascontiguousarray(halo, np.float32)).to(dev)
+        if halo_len is not None:
+            d_hl = torch.tensor([halo_len], dtype=torch.int64, device=dev)
+    engine.stft_power_device(t["slow"], t["flist"], t["len"], pn, t["win"], wlen, noverlap, nfft, FS, max_seg,
+                             t["P"] if store else None, t["pmax"], t["nseg"], d_halo=d_halo,
+                             n_halo=0 if halo is None else len(halo), d_halo_len=d_hl)
+    torch.cuda.synchronize()
+    return dict(n=int(t["nseg"].item()), P=t["P"].cpu().numpy(), pmax=np.float32(t["pmax"].item()), max_seg=max_seg, t=t)
+
+
+_GPU = {}
+
+
+def _gpu_case(engine, shape):
+    """The stored pass of a parity shape, run once and shared with the dB-stage tests (which only read it)."""
+    if shape not in _GPU:
+        x, w, _, _ = _ref(shape)
+        _GPU[shape] = _power(engine, x, w, shape[1], shape[2])
+    return _GPU[shape]
+
+
+def _db(p, pm):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return 20 * np.log10(np.asarray(p, np.float64) / np.float64(pm))
+
+
+def _assert_db_bar(got_db, ref_db, what):
+    """|got - ref| <= TOL_FP32_DB where ref >= -80 dB; elsewhere finite or -Inf and below the floor.
+    Prints the figure before it asserts."""
+    assert got_db.shape == ref_db.shape, what
+    sel = ref_db >= FLOOR
+    err = float(np.abs(got_db[sel] - ref_db[sel]).max()) if sel.any() else 0.0
+    print(f"STFT_ERR {what}: max |dB err| {err:.3e} over {sel.mean():.3f} of {ref_db.size} outputs")
+    assert sel.mean() >= 0.5, what
+    assert not np.isnan(got_db).any(), what
+    assert err <= TOL_FP32_DB, what
+    assert (got_db[~sel] <= FLOOR + TOL_FP32_DB).all(), what
+    return err
+
+
+# ---------------------------------------------------------------------------------------------------
+# parity of the stored P pass and of max(P)
+# ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", PARITY + [KAISER], ids=lambda s: "-".join(map(str, s)))
+def test_general_stft_power_meets_the_db_bar(engine, shape):
+    wlen, noverlap, nfft, L = shape
+    _, _, P, ref_db = _ref(shape)
+    r = _gpu_case(engine, shape)
+    n = P.shape[0]
+    assert r["n"] == n == R.nseg_of(L, wlen, noverlap)
+    assert np.isnan(r["P"][n:]).all()                                  # rows at and past nseg untouched
+    got = r["P"][:n]
+    assert np.isfinite(got).all() and (got >= 0).all()
+    assert r["pmax"] == got.max()                                       # max(P) is the maximum of what was stored
+    pm_err = abs(float(_db(r["pmax"], P.max())))
+    print(f"STFT_ERR k_stft_power {shape}: |dB err| of max(P) {pm_err:.3e}")
+    _assert_db_bar(_db(got, r["pmax"]), ref_db, f"k_stft_power {shape}")
+    assert pm_err <= TOL_FP32_DB
+
+
+# ---------------------------------------------------------------------------------------------------
+# the impulse known answer: fails when the window index is reversed
+# ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("wlen,noverlap,nfft,L,pos", [(256, 192, 300, 900, 400), (7, 2, 8, 60, 21)])
+def test_general_stft_impulse_known_answer(engine, wlen, noverlap, nfft, L, pos):
+    import torch
+    w = R.asym_window(wlen, 3)
+    x = np.zeros(L, np.float32)
+    x[pos] = 1.0
+    K = R.impulse_power(L, pos, w, noverlap, nfft, FS)
+    hit = K[:, 0] > 0
+    assert hit.sum() >= 2 and not hit.all()
+    r = _power(engine, x, w, noverlap, nfft)
+    n = K.shape[0]
+    assert r["n"] == n
+    got = r["P"][:n]
+    assert np.all(got[~hit] == 0)                                       # exactly 0 where the sample is missed
+    err = float(np.abs(_db(got[hit], 1.0) - _db(K[hit], 1.0)).max())
+    print(f"STFT_ERR k_stft_power impulse {(wlen, noverlap, nfft)}: max |dB err| {err:.3e}")
+    assert err <= TOL_FP32_DB
+    assert abs(float(_db(r["pmax"], K.max()))) <= TOL_FP32_DB
+    # through the dB stage the empty segments are -Inf, the others the known answer
+    t = r["t"]
+    out = torch.full_like(t["P"], np.nan)
+    engine.stft_db_device(t["P"], t["nseg"], r["max_seg"], nfft, FS, t["pmax"], 0, out)
+    torch.cuda.synchronize()
+    d = out.cpu().numpy()
+    assert np.isnan(d[n:]).all()
+    assert np.all(np.isneginf(d[:n][~hit]))
+    assert np.abs(d[:n][hit] - R.psd_db(K)[hit]).max() <= TOL_FP32_DB
+
+
+# ---------------------------------------------------------------------------------------------------
+# the compaction indirection and the right halo
+# ---------------------------------------------------------------------------------------------------
+def test_general_stft_reads_through_the_frame_list(engine):
+    """slow [5][50] read through frame_list [3, 0, 4] with a partial last frame: hop-1 segments of 32 taps
+    straddle both frame seams."""
+    wlen, noverlap, nfft, pn, L = 32, 31, 64, 50, 137
+    slow = R.magnitude_signal(5 * pn, 77).reshape(5, pn)
+    flist = [3, 0, 4]
+    x = np.concatenate([slow[f] for f in flist])[:L]
+    w = R.asym_window(wlen, 5)
+    P = R.stft_power(x, w, noverlap, nfft, FS)
+    r = _power(engine, x, w, noverlap, nfft, L=L, slow=slow, flist=flist, pn=pn)
+    assert r["n"] == P.shape[0] == L - noverlap
+    assert np.isnan(r["P"][r["n"]:]).all()
+    _assert_db_bar(_db(r["P"][:r["n"]], r["pmax"]), R.psd_db(P), "k_stft_power frame_list (32, 31, 64)")
+    assert abs(float(_db(r["pmax"], P.max()))) <= TOL_FP32_DB
+
+
+def test_general_stft_right_halo_with_device_length(engine):
+    """n_halo = 31 samples of halo buffer of which the device-held d_halo_len says 7 are valid: the signal
+    is concat(x, halo[:7]), read through a two-frame list."""
+    wlen, noverlap, nfft, pn, L = 32, 31, 64, 64, 100
+    slow = R.magnitude_signal(2 * pn, 78).reshape(2, pn)
+    flist = [1, 0]
+    x = np.concatenate([slow[1], slow[0]])[:L]
+    halo = R.magnitude_signal(31, 79) * 2
+    w = R.asym_window(wlen, 6)
+    P = R.stft_power(np.concatenate([x, halo[:7]]), w, noverlap, nfft, FS)
+    r = _power(engine, x, w, noverlap, nfft, L=L, slow=slow, flist=flist, pn=pn, halo=halo, halo_len=7)
+    assert r["n"] == P.shape[0] == L + 7 - noverlap
+    assert np.isnan(r["P"][r["n"]:]).all()
+    _assert_db_bar(_db(r["P"][:r["n"]], r["pmax"]), R.psd_db(P), "k_stft_power halo (32, 31, 64)")
+    assert abs(float(_db(r["pmax"], P.max()))) <= TOL_FP32_DB
+
+
+def test_general_stft_halo_needs_hop_1(engine):
+    from fmcw_radar_processing_amd import FmcwError
+    x = R.magnitude_signal(100, 1)
+    with pytest.raises(FmcwError, match="E_ARG"):
+        _power(engine, x, R.asym_window(32, 1), 30, 64, halo=np.ones(5, np.float32))
+
+
+# ---------------------------------------------------------------------------------------------------
+# clipping at max_seg, signals shorter than the window, the max-only pass, the running maximum
+# ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape,max_seg", [((32, 0, 32, 16000), 250), ((21, 20, 64, 300), 100), ((24, 12, 16384, 150), 1)],
+                         ids=["tile-seam", "hop1", "one-segment-tiles"])
+def test_general_stft_clips_at_max_seg(engine, shape, max_seg):
+    x, w, P, _ = _ref(shape)
+    full = _gpu_case(engine, shape)
+    assert max_seg < full["n"]
+    r = _power(engine, x, w, shape[1], shape[2], max_seg=max_seg)
+    assert r["n"] == max_seg
+    np.testing.assert_array_equal(r["P"][:max_seg], full["P"][:max_seg])     # bit for bit the unclipped rows
+    assert np.isnan(r["P"][max_seg:]).all()                                   # nothing past them
+    assert r["pmax"] == r["P"][:max_seg].max()
+
+
+@pytest.mark.parametrize("wlen,noverlap,nfft,L", [(32, 31, 64, 31), (256, 0, 300, 255), (1, 0, 2, 0), (20, 15, 64, 19)])
+def test_general_stft_signal_shorter_than_the_window(engine, wlen, noverlap, nfft, L):
+    x = R.magnitude_signal(max(wlen, 1), 3)                     # the buffer is longer than the L the device is told
+    r = _power(engine, x, R.asym_window(wlen, 2), noverlap, nfft, L=L, max_seg=4)
+    assert r["n"] == 0 and r["pmax"] == 0.0
+    assert np.isnan(r["P"]).all()
+
+
+@pytest.mark.parametrize("shape", [(5, 3, 6, 60), (32, 0, 32, 16000), (256, 128, 1000, 2000)], ids=lambda s: "-".join(map(str, s)))
+def test_general_stft_max_only_pass_is_the_stored_maximum(engine, shape):
+    x, w, _, _ = _ref(shape)
+    full = _gpu_case(engine, shape)
+    r = _power(engine, x, w, shape[1], shape[2], store=False)
+    assert r["n"] == full["n"]
+    assert r["pmax"].tobytes() == full["pmax"].tobytes()
+    assert np.isnan(r["P"]).all()
+
+
+def test_general_stft_never_lowers_the_running_maximum(engine):
+    shape = (64, 0, 100, 1000)
+    x, w, _, _ = _ref(shape)
+    big = _power(engine, x * np.float32(8), w, shape[1], shape[2], store=False)
+    again = _power(engine, x, w, shape[1], shape[2], store=False, pmax=big["t"]["pmax"])
+    assert again["pmax"] == big["pmax"] > _gpu_case(engine, shape)["pmax"] > 0
+
+
+# ---------------------------------------------------------------------------------------------------
+# arguments
+# ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("wlen,noverlap,nfft", [(257, 0, 512), (32, 32, 64), (32, 31, 63), (32, 31, 30), (0, 0, 64), (32, -1, 64)],
+                         ids=["wlen-257", "noverlap-wlen", "odd-nfft", "nfft-below-wlen", "wlen-0", "noverlap-negative"])
+def test_general_stft_rejects_bad_shapes(engine, wlen, noverlap, nfft):
+    from fmcw_radar_processing_amd import FmcwError
+    import torch
+    x = torch.ones((1, 1024), dtype=torch.float32, device="cuda")
+    win = torch.ones(max(wlen, 1), dtype=torch.float32, device="cuda")
+    flist = torch.zeros(1, dtype=torch.int32, device="cuda")
+    d_len = torch.tensor([1024], dtype=torch.int64, device="cuda")
+    d_P = torch.full((8, 1024), np.nan, dtype=torch.float32, device="cuda")
+    pmax = torch.zeros(1, dtype=torch.float32, device="cuda")
+    nseg = torch.full((1,), -1, dtype=torch.int64, device="cuda")
+    with pytest.raises(FmcwError, match="E_ARG"):
+        engine.stft_power_device(x, flist, d_len, 1024, win, wlen, noverlap, nfft, FS, 8, d_P, pmax, nseg)
+    torch.cuda.synchronize()
+    assert int(nseg.item()) == -1 and float(pmax.item()) == 0.0 and bool(torch.isnan(d_P).all())
+
+
+def test_direct_db_pass_rejects_a_21_tap_window(engine):
+    from fmcw_radar_processing_amd import FmcwError
+    import torch
+    x = torch.ones((1, 256), dtype=torch.float32, device="cuda")
+    win = torch.ones(21, dtype=torch.float32, device="cuda")
+    flist = torch.zeros(1, dtype=torch.int32, device="cuda")
+    d_len = torch.tensor([256], dtype=torch.int64, device="cuda")
+    out = torch.full((256, 33), np.nan, dtype=torch.float32, device="cuda")
+    pmax = torch.ones(1, dtype=torch.float32, device="cuda")
+    with pytest.raises(FmcwError, match="E_ARG"):
+        engine.stft_db_direct_device(x, flist, d_len, 256, win, 21, 20, 64, FS, 256, pmax, out)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(out).all())
+
+
+# ---------------------------------------------------------------------------------------------------
+# the dB stage behind the general kernel
+# ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", [(2, 1, 2, 40), (5, 3, 6, 60), (128, 121, 300, 1200)], ids=["nb-2", "nb-4", "nb-151"])
+def test_db_stage_linear_bins_three_forms(engine, shape):
+    """20 log10(P / max) in place, into an aligned buffer and into a 4-byte-offset slice (k_stft_db instead
+    of k_stft_db_flat): the same bits, and the dB bar against float64."""
+    import torch
+    nfft = shape[2]
+    _, _, _, ref_db = _ref(shape)
+    r = _gpu_case(engine, shape)
+    t, n, nb = r["t"], r["n"], nfft // 2 + 1
+    rows = t["P"].shape[0]
+    inplace = t["P"].clone()
+    sep = torch.full_like(t["P"], np.nan)
+    buf = torch.full((rows * nb + 1,), np.nan, dtype=torch.float32, device="cuda")
+    off = buf[1:]
+    assert inplace.data_ptr() % 16 == 0 and sep.data_ptr() % 16 == 0 and off.data_ptr() % 16 == 4
+    engine.stft_db_device(inplace, t["nseg"], r["max_seg"], nfft, FS, t["pmax"], 0, inplace)
+    engine.stft_db_device(t["P"], t["nseg"], r["max_seg"], nfft, FS, t["pmax"], 0, sep)
+    engine.stft_db_device(t["P"], t["nseg"], r["max_seg"], nfft, FS, t["pmax"], 0, off)
+    torch.cuda.synchronize()
+    a, b, c = inplace.cpu().numpy(), sep.cpu().numpy(), off.cpu().numpy().reshape(rows, nb)
+    assert np.isnan(b[n:]).all() and np.isnan(c[n:]).all() and np.isnan(a[n:]).all() and np.isnan(buf[:1].cpu().numpy()).all()
+    assert a[:n].tobytes() == b[:n].tobytes() == c[:n].tobytes()
+    np.testing.assert_array_equal(t["P"].cpu().numpy()[:n], r["P"][:n])          # the separate forms left P alone
+    _assert_db_bar(b[:n].astype(np.float64), ref_db, f"k_stft_db linear {shape[:3]}")
+
+
+@pytest.mark.parametrize("nlog", [1, 2, 7, 1024])
+@pytest.mark.parametrize("shape", [(2, 1, 2, 40), (5, 3, 6, 60), (64, 0, 100, 1000), (128, 121, 300, 1200)],
+                         ids=["nfft-2", "nfft-6", "nfft-100", "nfft-300"])
+def test_db_stage_log_resampling(engine, shape, nlog):
+    """interp1 onto n log bins against the oracle's, from the float64 dB map; held to the bar where both
+    source bins of an output are at or above the floor (an interpolated value inherits the error of its
+    two sources, and a source below the floor has no bound)."""
+    import torch
+    nfft = shape[2]
+    _, _, _, ref_db = _ref(shape)
+    r = _gpu_case(engine, shape)
+    t, n = r["t"], r["n"]
+    fq = R.log_freqs(nfft, FS, nlog)
+    want = O.log_resample(R.lin_freqs(nfft, FS), ref_db.T, fq).T
+    mine, i0 = R.log_resample(ref_db, nfft, FS, nlog)
+    np.testing.assert_allclose(want, mine, rtol=0, atol=1e-7)
+    out = torch.full((t["P"].shape[0], nlog), np.nan, dtype=torch.float32, device="cuda")
+    engine.stft_db_device(t["P"], t["nseg"], r["max_seg"], nfft, FS, t["pmax"], nlog, out)
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    assert np.isnan(got[n:]).all() and not np.isnan(got[:n]).any()
+    sel = (ref_db[:, i0] >= FLOOR) & (ref_db[:, i0 + 1] >= FLOOR)
+    err = float(np.abs(got[:n][sel] - want[sel]).max())
+    print(f"STFT_ERR k_stft_db log {shape[:3]} n_log_bins {nlog}: max |dB err| {err:.3e} over {sel.mean():.3f}")
+    assert sel.mean() >= 0.5
+    assert err <= TOL_FP32_DB
+
+
+def test_db_stage_rejects_in_place_resampling(engine):
+    from fmcw_radar_processing_amd import FmcwError
+    r = _gpu_case(engine, (5, 3, 6, 60))
+    t = r["t"]
+    with pytest.raises(FmcwError, match="E_ARG"):
+        engine.stft_db_device(t["P"], t["nseg"], r["max_seg"], 6, FS, t["pmax"], 7, t["P"])
+
+
+# ---------------------------------------------------------------------------------------------------
+# the host call
+# ---------------------------------------------------------------------------------------------------
+def _host_bar(got, ref, i0=None):
+    """got [nseg][nbins] float32 against the float64 map ref; with log bins only the outputs whose two
+    source bins (psd columns i0, i0 + 1) are at or above the floor carry the bar."""
+    gi, ri = got["intensity"], ref["intensity"]
+    assert gi.shape == ri.shape and gi.dtype == np.float32
+    sel = ri >= FLOOR
+    if i0 is not None:
+        sel &= (ref["psd"][:, i0] >= FLOOR) & (ref["psd"][:, i0 + 1] >= FLOOR)
+    err = float(np.abs(gi[sel] - ri[sel]).max())
+    print(f"STFT_ERR Engine.stft: max |dB err| {err:.3e} over {sel.mean():.3f} of {ri.size}")
+    assert sel.mean() >= 0.5 and not np.isnan(gi).any()
+    assert err <= TOL_FP32_DB
+
+
+@pytest.mark.parametrize("wlen,noverlap,nfft,nlog,L", [(33, 20, 0, 1024, 700), (7, 0, 8, 0, 100), (256, 192, 300, 16, 3000)])
+def test_host_stft_general_window(engine, wlen, noverlap, nfft, nlog, L):
+    x = R.magnitude_signal(L, L)
+    w = R.asym_window(wlen, 11)
+    got = engine.stft(x, w, noverlap, FS, nfft=nfft, n_log_bins=nlog)
+    nf = nfft or 2 ** O.nextpow2(L)
+    assert got["nfft"] == nf
+    ora = O.spectrogram_pipeline(x.astype(np.float64), 1 / FS, R.taps(w), noverlap, nfft=nfft or None, nbins=nlog)
+    assert ora["nfft"] == nf
+    np.testing.assert_allclose(got["time"], ora["time"], rtol=1e-6)
+    np.testing.assert_allclose(got["frequency"], ora["frequency"], rtol=1e-6)
+    ref = dict(intensity=ora["intensity"].T, psd=ora["psd"].T)
+    mine = R.pipeline(x, w, noverlap, nf, FS, nlog)
+    np.testing.assert_allclose(mine["intensity"], ref["intensity"], rtol=0, atol=1e-6)   # oracle and definition agree
+    _host_bar(got, ref, mine.get("i0"))
+
+
+@pytest.mark.parametrize("L,nseg", [(50, 2), (675, 50)])
+def test_host_stft_general_window_sharded(engine, L, nseg):
+    """Three contexts on one device: the host call's shard split at hop 13 (each shard's segment grid
+    starts at s0 hop), one shard empty when there are two segments; bit-identical to one context."""
+    from fmcw_radar_processing_amd.engine import Engine
+    wlen, noverlap, nfft = 33, 20, 64
+    assert R.nseg_of(L, wlen, noverlap) == nseg
+    x = R.magnitude_signal(L, L)
+    x[L // 2] *= 30                                             # the global maximum sits on one shard
+    w = R.asym_window(wlen, 12)
+    one = engine.stft(x, w, noverlap, FS, nfft=nfft, n_log_bins=0)
+    multi = Engine([0, 0, 0])
+    try:
+        got = multi.stft(x, w, noverlap, FS, nfft=nfft, n_log_bins=0)
+    finally:
+        multi.close()
+    assert got["nfft"] == one["nfft"] == nfft and got["intensity"].shape == (nseg, 33)
+    for k in ("time", "frequency", "intensity"):
+        assert got[k].tobytes() == one[k].tobytes(), k
+    _host_bar(one, dict(intensity=R.pipeline(x, w, noverlap, nfft, FS)["intensity"]))

@@ -9,6 +9,11 @@ An f32 MFMA is a k-ordered chain of f32 fmas, so each S(seg, bin) is the same ch
 (partial 16-segment groups and 256-segment blocks), hop 1 and 3, a right halo (the multi-GPU
 form), the P-storing pass, and the max-only pass followed by the direct dB pass.  Against the oracle the same path is held to
 the dB bar by tests/test_gpu_device_path.py.
+
+nfft 20, 22, 34, 66, 100 and 1000 leave the last 32-bin column chunk partial (its second 16-column
+tile empty, partly valid, or a second chunk of two columns) and are no powers of two: there the two
+table forms are also held to the float64 direct DFT of tests/stft_reference.py with an asymmetric
+window, since bit-identity between them says nothing about the W table they share.
 """
 import numpy as np
 import pytest
@@ -50,7 +55,13 @@ def _run(engine, monkeypatch, mfma, x, hop, halo, store, nfft=NFFT, fold=False, 
 @pytest.mark.parametrize("frames,hop,halo,store,nfft", [(3, 1, False, True, 64), (7, 1, True, True, 64),
                                                          (5, 3, False, True, 64), (9, 1, False, False, 64),
                                                          (40, 1, False, True, 64), (3, 1, False, True, 256),
-                                                         (5, 1, True, False, 2048), (4, 2, False, True, 512), (2, 1, False, True, 32)])
+                                                         (5, 1, True, False, 2048), (4, 2, False, True, 512), (2, 1, False, True, 32),
+                                                         # partial 32-bin column chunks and nfft that is no power of two:
+                                                         # 11 bins; 12 (the chunk's second 16-column tile empty); 18 (partly
+                                                         # valid); 34 (two columns in the second chunk); 51; 501
+                                                         (2, 1, False, True, 20), (2, 1, False, False, 22), (3, 3, False, True, 34),
+                                                         (2, 1, True, True, 66), (2, 1, False, False, 100), (2, 2, False, True, 1000),
+                                                         (2, 1, True, False, 1000), (2, 3, False, False, 66)])
 def test_mfma_stft_is_bit_identical(engine, monkeypatch, frames, hop, halo, store, nfft):
     rng = np.random.default_rng(frames * 10 + hop)
     # a slow-time magnitude signal: per-frame levels with noise, ragged length (a partial last frame)
@@ -148,3 +159,58 @@ def test_folded_stft64_short_signals(engine, monkeypatch, L):
     sel = dt >= -80
     assert np.abs(d1[sel] - dt[sel]).max() <= 1e-3
     assert (d1[~sel] <= -80 + 1e-3).all()
+
+
+@pytest.mark.parametrize("mfma", [True, False], ids=["k_stft_mfma", "k_stft20"])
+@pytest.mark.parametrize("nfft,hop,halo,store", [(20, 1, False, True), (22, 1, False, False), (34, 3, False, True),
+                                                 (66, 1, True, True), (66, 4, False, False), (100, 1, False, True),
+                                                 (100, 1, True, False), (1000, 1, False, True), (1000, 3, False, False)])
+def test_table_forms_meet_the_db_bar_at_any_nfft(engine, monkeypatch, mfma, nfft, hop, halo, store):
+    """Bit-identity of the two table forms says nothing about the W table itself: at an nfft that is no
+    power of two its phases come from stft_w's k m mod nfft.  Both forms against the float64 direct DFT
+    of tests/stft_reference.py with an asymmetric window, the stored pass and the direct dB pass, at
+    bin counts that leave the last 32-column chunk partial (11, 12, 18, 34, 51, 501)."""
+    from tests import stft_reference as R
+    from tests.helpers import TOL_FP32_DB
+    x = R.magnitude_signal(2 * PN, nfft + hop)
+    w = R.asym_window(WLEN, nfft)
+    hl = R.magnitude_signal(WLEN - 1, nfft + 7) * 2 if halo else None
+    n, p, m = _run(engine, monkeypatch, mfma, x, hop, hl, store, nfft, win=w)
+    P = R.stft_power(x if hl is None else np.concatenate([x, hl]), w, WLEN - hop, nfft, 1250.0)
+    assert n == P.shape[0]
+    dt = R.psd_db(P)
+    d1 = _db(p, m[0]) if store else p.astype(np.float64)
+    assert d1.shape == dt.shape and not np.isnan(d1).any()
+    sel = dt >= -80
+    err = float(np.abs(d1[sel] - dt[sel]).max())
+    pm_err = abs(float(_db(m, P.max())[0]))
+    print(f"STFT_ERR {'k_stft_mfma' if mfma else 'k_stft20'} {(WLEN, WLEN - hop, nfft)} {'P' if store else 'dB'}: "
+          f"max |dB err| {err:.3e} over {sel.mean():.3f}, max(P) {pm_err:.3e}")
+    assert sel.mean() >= 0.5
+    assert err <= TOL_FP32_DB and pm_err <= TOL_FP32_DB
+    assert (d1[~sel] <= -80 + TOL_FP32_DB).all()
+
+
+def test_host_stft_listed_bins_at_nfft_100(engine):
+    """Engine.stft with the 20-tap window, 1024 log bins and nfft 100: the listed-bins pass (mode 3) over
+    a table whose nfft is no power of two, against the oracle."""
+    from oracle import oracle as O
+    from tests import stft_reference as R
+    from tests.helpers import TOL_FP32_DB
+    x = R.magnitude_signal(600, 100)
+    w = R.asym_window(WLEN, 100)
+    got = engine.stft(x, w, WLEN - 1, 1250.0, nfft=100, n_log_bins=1024)
+    ref = O.spectrogram_pipeline(x.astype(np.float64), 1 / 1250.0, R.taps(w), WLEN - 1, nfft=100, nbins=1024)
+    assert got["nfft"] == ref["nfft"] == 100
+    np.testing.assert_allclose(got["time"], ref["time"], rtol=1e-6)
+    np.testing.assert_allclose(got["frequency"], ref["frequency"], rtol=1e-6)
+    ri, psd = ref["intensity"].T, ref["psd"].T
+    gi = got["intensity"]
+    assert gi.shape == ri.shape == (581, 1024) and not np.isnan(gi).any()
+    # an interpolated output inherits the error of its two source bins: both at or above the floor
+    _, i0 = R.log_resample(psd, 100, 1250.0, 1024)
+    sel = (ri >= -80) & (psd[:, i0] >= -80) & (psd[:, i0 + 1] >= -80)
+    err = float(np.abs(gi[sel] - ri[sel]).max())
+    print(f"STFT_ERR Engine.stft 20 taps nfft 100, 1024 log bins: max |dB err| {err:.3e} over {sel.mean():.3f}")
+    assert sel.mean() >= 0.5
+    assert err <= TOL_FP32_DB
