@@ -20,7 +20,7 @@ FMCW_PIPE_AUTO, FMCW_PIPE_STREAMS, FMCW_PIPE_ONEPASS, FMCW_PIPE_XCD = 0, 1, 3, 4
 ABI_VERSION = 4
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_HIP", -3: "E_OOM", -4: "E_STATE", -5: "E_DATA"}
 STAGES = ("range", "doppler", "detect", "compact", "stft_power", "stft_db", "range_only", "range_doppler", "onepass",
-          "render", "cfar")
+          "render", "cfar", "cluster")
 FMCW_CFAR_LOCAL_MAX = 1
 FMCW_SIG_DB = 1
 
@@ -56,6 +56,22 @@ class SigParams(ct.Structure):
         ("r_lo", ct.c_int32), ("r_hi", ct.c_int32), ("track_half", ct.c_int32), ("dc_half", ct.c_int32),
         ("flags", ct.c_int32), ("floor_db", ct.c_float),
     ]
+
+
+class ClusterParams(ct.Structure):
+    """fmcw_cluster_params (include/fmcw.h)."""
+    _fields_ = [("link_r", ct.c_int32), ("link_d", ct.c_int32), ("min_cells", ct.c_int32), ("max_tgt", ct.c_int32),
+                ("flags", ct.c_int32)]
+
+
+class Targets(ct.Structure):
+    """fmcw_targets (include/fmcw.h): output pointers, [F][max_tgt] each but tgt_count [F]."""
+    _fields_ = [(k, ct.c_void_p) for k in ("tgt_count", "cells", "peak_range_idx", "peak_doppler_idx", "extent_r",
+                                           "extent_d", "peak_power", "peak_noise", "power", "range", "doppler")]
+
+
+TARGET_INT_KEYS = ("cells", "peak_range_idx", "peak_doppler_idx", "extent_r", "extent_d")
+TARGET_FLOAT_KEYS = ("peak_power", "peak_noise", "power", "range", "doppler")
 
 
 class JsonField(ct.Structure):
@@ -114,6 +130,11 @@ SIGNATURES = {
     "fmcw_sig_device": (ct.c_int, [_P, ct.POINTER(SigParams), _P, _I32, _I64, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P]),
     "fmcw_sig_db_device": (ct.c_int, [_P, _P, _I64, _P, _F, _P, _P]),
     "fmcw_sig": (ct.c_int, [_P, ct.POINTER(SigParams), _P, _I32, _I64, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
+    "fmcw_cluster_check": (ct.c_int, [ct.POINTER(ClusterParams), _I32, _I32, _I32]),
+    "fmcw_cluster_device": (ct.c_int, [_P, ct.POINTER(ClusterParams), _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P,
+                                       ct.POINTER(Targets), _P, _P]),
+    "fmcw_cluster": (ct.c_int, [_P, ct.POINTER(ClusterParams), _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P,
+                                ct.POINTER(Targets), _P]),
     "fmcw_json_write": (ct.c_int, [ct.c_char_p, ct.POINTER(JsonField), _I32, _I32, _I32, ct.POINTER(_I64)]),
     "fmcw_stft_png": (ct.c_int, [_P, _P, _I64, _P, _I32, _I32, _I32, _D, _I32, _P, _P, _P, ct.c_char_p, _I32, _I32,
                                  ct.POINTER(_I64)]),

@@ -177,7 +177,7 @@ void shard(int64_t total, int g, int world, int64_t& f0, int64_t& n) {
   n = base + (g < rem ? 1 : 0);
 }
 
-constexpr int kStages = 11;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar
+constexpr int kStages = 12;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar, 11 cluster
 
 }  // namespace
 
@@ -328,6 +328,8 @@ struct fmcw_ctx {
   PerStream sig_scr;
   // fmcw_sig (host pointers): the RD chunk, the centres, and both maps with their two maxima on the device
   DevBuf sg_in, sg_ctr, sg_out;
+  // fmcw_cluster (host pointers): the chunk's detection lists and the per-frame outputs on the device
+  DevBuf cl_in, cl_out;
   int64_t chunk_frames = 0;
   int64_t last_coarse_tiles = -1;     // tiles the last coarse-to-fine max(P) evaluated in full (diagnostics)
   int pipe_mode = FMCW_PIPE_AUTO;
@@ -2372,6 +2374,166 @@ int fmcw_sig(fmcw_ctx* c, const fmcw_sig_params* q, const void* rd, int32_t rd_d
   return over_devices(c, F, [&](fmcw_ctx* d, int, int64_t f0, int64_t n) {
     return sig_host_finish(d, n, nr, nd, db, gmx, q->floor_db, doppler_time ? doppler_time + f0 * nd : nullptr,
                            range_time ? range_time + f0 * nr : nullptr);
+  });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Targets from the CFAR detection lists (kernels_cluster.hip)
+// ---------------------------------------------------------------------------
+static int cluster_check_impl(const fmcw_cluster_params* q, int32_t nr, int32_t nd, int32_t max_det) {
+  if (!q) return fail(FMCW_E_ARG, "cluster params is NULL");
+  if (nr < 16 || nr > 2048 || (nr & (nr - 1))) return fail(FMCW_E_ARG, "cluster: nr must be a power of two in [16, 2048]");
+  if (nd < 4 || nd > 1024 || (nd & (nd - 1))) return fail(FMCW_E_ARG, "cluster: nd must be a power of two in [4, 1024]");
+  if (q->link_r < 0 || q->link_r > 8 || q->link_d < 0 || q->link_d > 8)
+    return fail(FMCW_E_ARG, "cluster: link_r and link_d must be in [0, 8]");
+  if (2 * q->link_d + 1 > nd) return fail(FMCW_E_ARG, "cluster: the Doppler link 2 link_d + 1 exceeds nd");
+  if (q->min_cells < 1 || q->min_cells > 1024) return fail(FMCW_E_ARG, "cluster: min_cells must be in [1, 1024]");
+  if (q->max_tgt < 1 || q->max_tgt > 64) return fail(FMCW_E_ARG, "cluster: max_tgt must be in [1, 64]");
+  if (max_det < 1 || max_det > 1024) return fail(FMCW_E_ARG, "cluster: max_det must be in [1, 1024]");
+  if (q->flags != 0) return fail(FMCW_E_ARG, "cluster: unknown flag bits");
+  return FMCW_OK;
+}
+
+namespace {
+// byte offsets of one shard's outputs in the context's cl_out: the fmcw_targets members in
+// declaration order, then det_label
+struct ClusterOut {
+  size_t o[12], bytes;
+  ClusterOut(int64_t F, int M, int K) {
+    Arena ar;
+    o[0] = ar.add((size_t)F * 4);
+    for (int i = 1; i < 11; ++i) o[i] = ar.add((size_t)F * M * 4);
+    o[11] = ar.add((size_t)F * K * 4);
+    bytes = ar.off;
+  }
+};
+}  // namespace
+
+static int cluster_host_one(fmcw_ctx* c, const fmcw_cluster_params* q, int64_t F, int32_t nr, int32_t nd, int32_t K,
+                            const int32_t* count, const int32_t* ridx, const int32_t* didx, const float* power,
+                            const float* noise, const fmcw_targets& out, int32_t* label) {
+  CHK(set_device(c));
+  hipStream_t s = c->stream;
+  const int M = q->max_tgt;
+  const size_t flist = (size_t)K * 4;
+  const int64_t Fc = host_chunk(4 + 4 * flist, F);
+  const ClusterOut co(F, M, K);
+  Arena in;
+  const size_t i_count = in.add((size_t)Fc * 4), i_ridx = in.add((size_t)Fc * flist), i_didx = in.add((size_t)Fc * flist),
+               i_pow = in.add((size_t)Fc * flist), i_noise = in.add((size_t)Fc * flist);
+  CHK(c->cl_out.ensure(co.bytes));
+  CHK(c->cl_in.ensure(in.off));
+  char* const o = c->cl_out.as<char>();
+  char* const di = c->cl_in.as<char>();
+  void* const host[12] = {out.tgt_count, out.cells, out.peak_range_idx, out.peak_doppler_idx, out.extent_r, out.extent_d,
+                          out.peak_power, out.peak_noise, out.power, out.range, out.doppler, label};
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    const int64_t nf = std::min(Fc, F - f0);
+    HIPCHK(hipMemcpyAsync(di + i_count, count + f0, (size_t)nf * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(di + i_ridx, ridx + f0 * K, (size_t)nf * flist, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(di + i_didx, didx + f0 * K, (size_t)nf * flist, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(di + i_pow, power + f0 * K, (size_t)nf * flist, hipMemcpyHostToDevice, s));
+    if (noise) HIPCHK(hipMemcpyAsync(di + i_noise, noise + f0 * K, (size_t)nf * flist, hipMemcpyHostToDevice, s));
+    fmcw_targets d{};
+    d.tgt_count = reinterpret_cast<int32_t*>(o + co.o[0]) + f0;
+    int32_t** const ip[5] = {&d.cells, &d.peak_range_idx, &d.peak_doppler_idx, &d.extent_r, &d.extent_d};
+    float** const fp[5] = {&d.peak_power, &d.peak_noise, &d.power, &d.range, &d.doppler};
+    for (int i = 0; i < 5; ++i) {
+      *ip[i] = host[1 + i] ? reinterpret_cast<int32_t*>(o + co.o[1 + i]) + f0 * M : nullptr;
+      *fp[i] = host[6 + i] ? reinterpret_cast<float*>(o + co.o[6 + i]) + f0 * M : nullptr;
+    }
+    CHK(fmcw_cluster_device(c, q, nf, nr, nd, K, reinterpret_cast<int32_t*>(di + i_count),
+                            reinterpret_cast<int32_t*>(di + i_ridx), reinterpret_cast<int32_t*>(di + i_didx),
+                            reinterpret_cast<float*>(di + i_pow), noise ? reinterpret_cast<float*>(di + i_noise) : nullptr,
+                            &d, label ? reinterpret_cast<int32_t*>(o + co.o[11]) + f0 * K : nullptr, s));
+    HIPCHK(hipStreamSynchronize(s));           // the chunk buffers are reused by the next chunk
+  }
+  for (int i = 0; i < 12; ++i) {
+    if (!host[i]) continue;
+    const size_t bytes = (size_t)F * 4 * (i == 0 ? 1 : i == 11 ? K : M);
+    HIPCHK(hipMemcpyAsync(host[i], o + co.o[i], bytes, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  return FMCW_OK;
+}
+
+extern "C" {
+
+int fmcw_cluster_check(const fmcw_cluster_params* q, int32_t nr, int32_t nd, int32_t max_det) {
+  return cluster_check_impl(q, nr, nd, max_det);
+}
+
+int fmcw_cluster_device(fmcw_ctx* c, const fmcw_cluster_params* q, int64_t F, int32_t nr, int32_t nd, int32_t max_det,
+                        const int32_t* d_count, const int32_t* d_ridx, const int32_t* d_didx, const float* d_power,
+                        const float* d_noise, const fmcw_targets* d_out, int32_t* d_label, void* stream) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(cluster_check_impl(q, nr, nd, max_det));
+  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
+  if (F == 0) return FMCW_OK;
+  if (!d_count || !d_ridx || !d_didx || !d_power || !d_out || !d_out->tgt_count)
+    return fail(FMCW_E_ARG, "required pointer is NULL");
+  CHK(set_device(c));
+  hipStream_t s = pick(c, stream);
+  fmcw::ClusterArgs a{};
+  a.ND = nd;
+  a.K = max_det;
+  a.link_r = q->link_r; a.link_d = q->link_d; a.min_cells = q->min_cells; a.max_tgt = q->max_tgt;
+  const int64_t K = max_det, M = q->max_tgt;
+  // one workgroup per frame: at most 2^20 frames per launch (the results do not depend on the cut)
+  const int64_t Fc = (int64_t)1 << 20;
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    a.F = std::min(Fc, F - f0);
+    a.det_count = d_count + f0;
+    a.det_ridx = d_ridx + f0 * K;
+    a.det_didx = d_didx + f0 * K;
+    a.det_power = d_power + f0 * K;
+    a.det_noise = d_noise ? d_noise + f0 * K : nullptr;
+    a.tgt_count = d_out->tgt_count + f0;
+    a.cells = d_out->cells ? d_out->cells + f0 * M : nullptr;
+    a.pk_ridx = d_out->peak_range_idx ? d_out->peak_range_idx + f0 * M : nullptr;
+    a.pk_didx = d_out->peak_doppler_idx ? d_out->peak_doppler_idx + f0 * M : nullptr;
+    a.ext_r = d_out->extent_r ? d_out->extent_r + f0 * M : nullptr;
+    a.ext_d = d_out->extent_d ? d_out->extent_d + f0 * M : nullptr;
+    a.pk_power = d_out->peak_power ? d_out->peak_power + f0 * M : nullptr;
+    a.pk_noise = d_out->peak_noise ? d_out->peak_noise + f0 * M : nullptr;
+    a.power = d_out->power ? d_out->power + f0 * M : nullptr;
+    a.range = d_out->range ? d_out->range + f0 * M : nullptr;
+    a.doppler = d_out->doppler ? d_out->doppler + f0 * M : nullptr;
+    a.det_label = d_label ? d_label + f0 * K : nullptr;
+    StageTimer tm(c, 11, s);
+    HIPCHK(fmcw::launch_cluster(a, s));
+    tm.done();
+  }
+  return FMCW_OK;
+}
+
+int fmcw_cluster(fmcw_ctx* c, const fmcw_cluster_params* q, int64_t F, int32_t nr, int32_t nd, int32_t max_det,
+                 const int32_t* count, const int32_t* ridx, const int32_t* didx, const float* power, const float* noise,
+                 const fmcw_targets* out, int32_t* label) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(cluster_check_impl(q, nr, nd, max_det));
+  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
+  if (F == 0) return FMCW_OK;
+  if (!count || !ridx || !didx || !power || !out || !out->tgt_count) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const int64_t K = max_det, M = q->max_tgt;
+  // frames are independent: contiguous shards, each written in place
+  return over_devices(c, F, [&](fmcw_ctx* d, int, int64_t f0, int64_t n) {
+    fmcw_targets t{};
+    t.tgt_count = out->tgt_count + f0;
+    t.cells = out->cells ? out->cells + f0 * M : nullptr;
+    t.peak_range_idx = out->peak_range_idx ? out->peak_range_idx + f0 * M : nullptr;
+    t.peak_doppler_idx = out->peak_doppler_idx ? out->peak_doppler_idx + f0 * M : nullptr;
+    t.extent_r = out->extent_r ? out->extent_r + f0 * M : nullptr;
+    t.extent_d = out->extent_d ? out->extent_d + f0 * M : nullptr;
+    t.peak_power = out->peak_power ? out->peak_power + f0 * M : nullptr;
+    t.peak_noise = out->peak_noise ? out->peak_noise + f0 * M : nullptr;
+    t.power = out->power ? out->power + f0 * M : nullptr;
+    t.range = out->range ? out->range + f0 * M : nullptr;
+    t.doppler = out->doppler ? out->doppler + f0 * M : nullptr;
+    return cluster_host_one(d, q, n, nr, nd, max_det, count + f0, ridx + f0 * K, didx + f0 * K, power + f0 * K,
+                            noise ? noise + f0 * K : nullptr, t, label ? label + f0 * K : nullptr);
   });
 }
 

@@ -344,6 +344,25 @@ size_t sig_scratch_per_frame(const SigArgs& a);
 hipError_t launch_sig(const SigArgs& a, hipStream_t s);
 hipError_t launch_sig_db(const float* map, int64_t n, const float* mx, float floor_db, float* out, hipStream_t s);
 
+// Clustering of the CFAR detection lists into targets (kernels_cluster.hip): k_cluster
+struct ClusterArgs {
+  int64_t F;
+  int ND;                  // Doppler ring length (a power of two)
+  int K;                   // max_det: entries per frame of the lists
+  int link_r, link_d, min_cells, max_tgt;
+  const int32_t* det_count;        // [F]
+  const int32_t* det_ridx;         // [F][K]
+  const int32_t* det_didx;         // [F][K]
+  const float* det_power;          // [F][K]
+  const float* det_noise;          // [F][K] or nullptr
+  int32_t* tgt_count;              // [F]
+  // [F][max_tgt] each, any may be nullptr
+  int32_t* cells; int32_t* pk_ridx; int32_t* pk_didx; int32_t* ext_r; int32_t* ext_d;
+  float* pk_power; float* pk_noise; float* power; float* range; float* doppler;
+  int32_t* det_label;              // [F][K] or nullptr
+};
+hipError_t launch_cluster(const ClusterArgs& a, hipStream_t s);
+
 bool range_size_supported(int nr);
 bool doppler_size_supported(int nd);
 

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import FMCW_C32H, FMCW_C64, STAGES, FmcwError, check
-from .params import CfarConfig, FmcwConfig, SigConfig
+from .params import CfarConfig, ClusterConfig, FmcwConfig, SigConfig
 
 
 def _ptr(a) -> ct.c_void_p:
@@ -365,6 +365,80 @@ class Engine:
                               sig_outs.get("range_time"), sig_outs.get("dt_max"), sig_outs.get("rt_max"),
                               d_center=outs["tgt_range_idx"] if track else None, center_stride=cfg.max_targets,
                               stream=stream)
+
+    # ---- targets from the CFAR detection lists (include/fmcw.h, fmcw_cluster_params) ----------
+    def cluster(self, det: dict, q: ClusterConfig, nr: int, nd: int) -> dict:
+        """Targets of the detection lists `det` (the dict Engine.cfar returns, or any dict with
+        det_count [F], det_range_idx, det_doppler_idx, det_power [F][max_det] and, optionally,
+        det_noise).  Host arrays, sharded over the context's devices.  Returns tgt_count [F]; cells,
+        peak_range_idx, peak_doppler_idx, extent_r, extent_d (int32) and peak_power, peak_noise,
+        power, range, doppler (float32), each [F][max_tgt] with 1-based indices and 0 where unused;
+        det_label [F][max_det]; and, once set_taps has given the geometry's scales, range_m /
+        speed_mps of the centroids (NaN where unused)."""
+        cnt = np.ascontiguousarray(det["det_count"], np.int32)
+        ridx = np.ascontiguousarray(det["det_range_idx"], np.int32)
+        didx = np.ascontiguousarray(det["det_doppler_idx"], np.int32)
+        pw = np.ascontiguousarray(det["det_power"], np.float32)
+        noise = det.get("det_noise")
+        noise = None if noise is None else np.ascontiguousarray(noise, np.float32)
+        F = cnt.shape[0]
+        if ridx.ndim != 2 or ridx.shape[0] != F or didx.shape != ridx.shape or pw.shape != ridx.shape or \
+                (noise is not None and noise.shape != ridx.shape):
+            raise ValueError("the detection lists must be [F][max_det], det_count [F]")
+        K, M = ridx.shape[1], int(q.max_tgt)
+        out = dict(tgt_count=np.zeros(F, np.int32))
+        for k in _lib.TARGET_INT_KEYS:
+            out[k] = np.zeros((F, max(M, 0)), np.int32)
+        for k in _lib.TARGET_FLOAT_KEYS:
+            out[k] = np.zeros((F, max(M, 0)), np.float32)
+        out["det_label"] = np.zeros((F, K), np.int32)
+        qa = q.abi()
+        t = _lib.Targets(*[_ptr(out[k]) for k, _ in _lib.Targets._fields_])
+        check(self.lib.fmcw_cluster(self.h, ct.byref(qa), F, int(nr), int(nd), K, _ptr(cnt), _ptr(ridx), _ptr(didx),
+                                    _ptr(pw), _ptr(noise), ct.byref(t), _ptr(out["det_label"])))
+        if self.cfg is not None and (self.cfg.nr, self.cfg.nd) == (int(nr), int(nd)):
+            used = out["cells"] > 0
+            out["range_m"] = np.where(used, self.cfg.range_m(out["range"]), np.nan)
+            out["speed_mps"] = np.where(used, self.cfg.speed(out["doppler"]), np.nan)
+        return out
+
+    def cluster_device(self, q: ClusterConfig, F: int, nr: int, nd: int, max_det: int, det: dict, outs: dict,
+                       d_det_label=None, stream=None) -> None:
+        """fmcw_cluster_device: det holds the device buffers fmcw_cfar_device wrote (det_count,
+        det_range_idx, det_doppler_idx, det_power and, optionally, det_noise); outs the device
+        buffers tgt_count [F] int32 and any of cells, peak_range_idx, peak_doppler_idx, extent_r,
+        extent_d (int32), peak_power, peak_noise, power, range, doppler (float32), [F][max_tgt]
+        each (missing or None: not written); d_det_label [F][max_det] int32 or None.  q: a
+        ClusterConfig, or the C struct _lib.ClusterParams itself.  Asynchronous on `stream`."""
+        qa = q.abi() if hasattr(q, "abi") else q
+        t = _lib.Targets(*[_ptr(outs.get(k)) for k, _ in _lib.Targets._fields_])
+        with _sided(stream) as hs:
+            check(self.lib.fmcw_cluster_device(self.h, ct.byref(qa), int(F), int(nr), int(nd), int(max_det),
+                                               _ptr(det["det_count"]), _ptr(det["det_range_idx"]),
+                                               _ptr(det["det_doppler_idx"]), _ptr(det["det_power"]),
+                                               _ptr(det.get("det_noise")), ct.byref(t), _ptr(d_det_label), hs))
+
+    def targets(self, rd: np.ndarray, q_cfar: CfarConfig, q_cluster: ClusterConfig) -> dict:
+        """cfar then cluster over rd (host arrays): the dict of `cluster`, with the detection lists
+        of `cfar` under their own names."""
+        det = self.cfar(rd, q_cfar)
+        nr, nd = rd.shape[1:3]
+        out = self.cluster(det, q_cluster, nr, nd)
+        for k in ("det_count", "det_range_idx", "det_doppler_idx", "det_power", "det_noise"):
+            out[k] = det[k]
+        return out
+
+    def process_targets_device(self, d_iq, F: int, in_dtype: int, outs: dict, q_cfar: CfarConfig, d_rd,
+                               cfar_outs: dict, q_cluster: ClusterConfig, tgt_outs: dict, d_det_label=None,
+                               out_dtype: int = FMCW_C64, d_mask=None, d_cube=None, probe_column: int = 0,
+                               stream=None) -> None:
+        """IQ in, targets out, on one stream with no host round trip: process_cfar_device (RD map to
+        d_rd, detection lists to cfar_outs), then cluster_device over those lists into tgt_outs."""
+        cfg = self._need()
+        self.process_cfar_device(d_iq, F, in_dtype, outs, q_cfar, d_rd, cfar_outs, out_dtype=out_dtype, d_mask=d_mask,
+                                 d_cube=d_cube, probe_column=probe_column, stream=stream)
+        self.cluster_device(q_cluster, F, cfg.nr, cfg.nd, q_cfar.max_det, cfar_outs, tgt_outs,
+                            d_det_label=d_det_label, stream=stream)
 
     # ---- timing -----------------------------------------------------------------
     def timing(self, level: int) -> None:

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import windows
-from ._lib import FMCW_CFAR_LOCAL_MAX, FMCW_SIG_DB, CfarParams, Params, SigParams
+from ._lib import FMCW_CFAR_LOCAL_MAX, FMCW_SIG_DB, CfarParams, ClusterParams, Params, SigParams
 
 C0 = 3e8  # radar_processing.m:67
 
@@ -209,6 +209,47 @@ class SigConfig:
         g = CfarConfig.for_config(cfg)
         return cls(r_lo=g.r_lo, r_hi=g.r_hi, track_half=int(track_half), dc_half=int(dc_half), db=bool(db),
                    floor_db=float(floor_db))
+
+
+@dataclass
+class ClusterConfig:
+    """fmcw_cluster_params (include/fmcw.h): groups the CFAR detection lists into targets.  Cells
+    within link_r range bins and link_d (circular) Doppler bins of each other are linked, (1, 1) being
+    8-connectivity; clusters of fewer than min_cells cells are dropped; the max_tgt targets of the
+    largest peak power are written per frame."""
+    link_r: int = 1
+    link_d: int = 1
+    min_cells: int = 1
+    max_tgt: int = 16
+
+    def abi(self) -> ClusterParams:
+        return ClusterParams(self.link_r, self.link_d, self.min_cells, self.max_tgt, 0)
+
+    def validate(self, nr: int, nd: int, max_det: int) -> None:
+        """The rules of fmcw_cluster_check; ValueError naming the first one violated."""
+        if nr < 16 or nr > 2048 or nr & (nr - 1):
+            raise ValueError("cluster: nr must be a power of two in [16, 2048]")
+        if nd < 4 or nd > 1024 or nd & (nd - 1):
+            raise ValueError("cluster: nd must be a power of two in [4, 1024]")
+        if not (0 <= self.link_r <= 8 and 0 <= self.link_d <= 8):
+            raise ValueError("cluster: link_r and link_d must be in [0, 8]")
+        if 2 * self.link_d + 1 > nd:
+            raise ValueError("cluster: the Doppler link 2 link_d + 1 exceeds nd")
+        if not 1 <= self.min_cells <= 1024:
+            raise ValueError("cluster: min_cells must be in [1, 1024]")
+        if not 1 <= self.max_tgt <= 64:
+            raise ValueError("cluster: max_tgt must be in [1, 64]")
+        if not 1 <= max_det <= 1024:
+            raise ValueError("cluster: max_det must be in [1, 1024]")
+
+    @classmethod
+    def for_config(cls, cfg: "FmcwConfig", link=(1, 1), min_cells: int = 2, max_tgt: int = 16,
+                   max_det: int = 64) -> "ClusterConfig":
+        """The clustering for cfg's RD map and lists of max_det entries (CfarConfig.for_config's
+        default): 8-connectivity, single-cell clusters (isolated false alarms) dropped."""
+        q = cls(link_r=int(link[0]), link_d=int(link[1]), min_cells=int(min_cells), max_tgt=int(max_tgt))
+        q.validate(cfg.nr, cfg.nd, int(max_det))
+        return q
 
 
 def derive_params(device: dict, nr: int = 256, nd: int = 16, mode: str = PARITY, **over) -> FmcwConfig:

@@ -43,7 +43,10 @@ extern "C" {
  * 4: + the CFAR entry points (fmcw_cfar_check, fmcw_cfar_alpha, fmcw_cfar_device, fmcw_cfar)
  *    and timing stage 10, added within ABI 4: nothing that existed changed
  *    + the signature entry points (fmcw_sig_check, fmcw_sig_device, fmcw_sig_db_device,
- *    fmcw_sig), added within ABI 4 in the same way */
+ *    fmcw_sig), added within ABI 4 in the same way
+ *    + the clustering entry points (fmcw_cluster_check, fmcw_cluster_device, fmcw_cluster), the
+ *    structs fmcw_cluster_params / fmcw_targets and timing stage 11, added within ABI 4 in the
+ *    same way */
 #define FMCW_ABI_VERSION 4
 
 typedef enum fmcw_status {
@@ -269,7 +272,8 @@ int fmcw_synth_device(fmcw_ctx* ctx, const fmcw_params* p, int64_t frame0, int64
  * stage: 0 range, 1 doppler, 2 detect, 3 compact, 4 stft_power, 5 stft_db,
  *        6 range_only, 7 range+Doppler span, 8 k_rdx (single-pass schedule,
  *        level 2), 9 render (spectrogram.png), 10 cfar (one pair per k_cfar + k_cfar_gather
- *        launch pair of fmcw_cfar_device).  fmcw_timing_read synchronises. */
+ *        launch pair of fmcw_cfar_device), 11 cluster (one pair per k_cluster launch of
+ *        fmcw_cluster_device).  fmcw_timing_read synchronises. */
 int fmcw_timing_enable(fmcw_ctx* ctx, int32_t enable);
 int fmcw_timing_read(fmcw_ctx* ctx, int32_t stage, double* total_ms, int64_t* launches);
 int fmcw_timing_reset(fmcw_ctx* ctx);
@@ -438,6 +442,89 @@ int fmcw_sig_db_device(fmcw_ctx* ctx, const float* d_map, int64_t n, const float
 int fmcw_sig(fmcw_ctx* ctx, const fmcw_sig_params* q, const void* rd, int32_t rd_dtype, int64_t F,
              int32_t nr, int32_t nd, const int32_t* center, int32_t center_stride, float* doppler_time,
              float* range_time, float* dt_max, float* rt_max);
+
+/* ---------------------------------------------------------------------------
+ * Targets from the CFAR detection lists: clustering, centroids, extents (added within ABI 4;
+ * the reference's product is one range and one speed per target and frame, range_speed of
+ * :241-252 / :385-389, which it takes from the one-peak rule; this stage forms it from the CFAR
+ * cells).  It works on the lists fmcw_cfar* wrote, never on the RD map or the mask: O(F max_det)
+ * bytes, no RD dtype.  Every index is 1-based.
+ *   Input of frame f: the first n = clamp(det_count[f], 0, max_det) entries of det_range_idx,
+ *     det_doppler_idx, det_power [F][max_det] and, optionally, det_noise, exactly as fmcw_cfar*
+ *     writes them: ascending (range, Doppler), powers finite and >= 0.  det_count[f] > max_det
+ *     means the list was cut: the targets are those of its first max_det cells.  On input that
+ *     breaks this the result is unspecified, but nothing is read or written out of bounds (the
+ *     indices are only ever compared, never used as addresses) and the call still ends.
+ *   Linking: cells i, j are linked iff |r_i - r_j| <= link_r and
+ *     min(|d_i - d_j|, nd - |d_i - d_j|) <= link_d (Doppler is circular, range is not, as in
+ *     CFAR).  (1, 1) is 8-connectivity; (0, 0) makes every cell its own cluster.  A cluster is a
+ *     connected component of this graph; its label is the smallest list index in it.
+ *   Per cluster, every sum in ascending list order, delta_i = ((d_i - d_pk + nd/2) mod nd) - nd/2:
+ *     cells             the member count
+ *     peak_range_idx, peak_doppler_idx, peak_power, peak_noise
+ *                       the member with the largest det_power (ties: the smallest list index);
+ *                       peak_noise is its det_noise, 0 without that array
+ *     power             sum of P_i
+ *     range             r_pk + sum P_i (r_i - r_pk) / power          (r_pk where power is 0)
+ *     doppler           d_pk + sum P_i delta_i / power, brought into [0.5, nd + 0.5) by +- nd
+ *     extent_r          r_max - r_min + 1
+ *     extent_d          max delta - min delta + 1
+ *   Clusters with cells < min_cells are dropped; the rest are ordered by peak_power descending,
+ *   ties by label ascending.  tgt_count[f] is their full number (it may exceed max_tgt); the first
+ *   max_tgt are written, unused entries are 0 in every array.
+ *   det_label [F][max_det] i32 (optional): entry i < n gets the 1-based place of its target in
+ *   that order (it may exceed max_tgt), 0 when its cluster was dropped; unused entries get 0.
+ *   Constraints: link_r, link_d in 0..8; 2 link_d + 1 <= nd; min_cells in 1..1024; max_tgt in
+ *     1..64; max_det in 1..1024; nr, nd within CFAR's limits; flags 0 (no bit is defined).
+ *   Results are bit-identical from call to call and do not depend on F or on how a host call is
+ *   sharded or chunked: integer steps decide the partition, the peak and the order, and the sums
+ *   are formed one member after the other in list order (no float atomics).  power is within
+ *   (n + 8) 2^-24 relative of the exact sum, n the cluster's cell count.
+ *   Measured on one MI355X on the CFAR lists of 4096 frames of 1024 x 256, link (1, 1), min_cells 2,
+ *   max_tgt 16 (profiles/cluster_bench.json, 2026-10-19, tree 72a1213+): 0.018 ms at 12.5 cells per
+ *   frame (pfa 1e-6, max_det 64) and 0.208 ms at 476 cells per frame (pfa 1e-3, max_det 1024), beside
+ *   8.36 / 10.17 ms for the fmcw_cfar_device call that wrote the lists and 0.005 / 0.014 ms for
+ *   fmcw_copy_device over the bytes the stage reads and writes, in the same run.
+ * ------------------------------------------------------------------------- */
+typedef struct fmcw_cluster_params {
+  int32_t link_r, link_d;  /* 0..8 */
+  int32_t min_cells;       /* 1..1024 */
+  int32_t max_tgt;         /* 1..64 */
+  int32_t flags;           /* 0 */
+} fmcw_cluster_params;
+
+/* Output pointers, [F][max_tgt] each but tgt_count [F]; any member except tgt_count may be NULL. */
+typedef struct fmcw_targets {
+  int32_t* tgt_count;
+  int32_t* cells;
+  int32_t* peak_range_idx;
+  int32_t* peak_doppler_idx;
+  int32_t* extent_r;
+  int32_t* extent_d;
+  float*   peak_power;
+  float*   peak_noise;
+  float*   power;
+  float*   range;
+  float*   doppler;
+} fmcw_targets;
+
+/* Host only, no context: FMCW_E_ARG (with a message) for any violation of the constraints. */
+int fmcw_cluster_check(const fmcw_cluster_params* q, int32_t nr, int32_t nd, int32_t max_det);
+
+/* Device pointers (the members of *d_out are device pointers, the struct itself is read on the host),
+ * asynchronous on `stream`; needs no fmcw_set_taps.  Acts on the context's first device.  F = 0 is a
+ * no-op.  FMCW_E_ARG is returned before any launch: the outputs are then untouched.  d_det_noise and
+ * d_det_label may be NULL. */
+int fmcw_cluster_device(fmcw_ctx* ctx, const fmcw_cluster_params* q, int64_t F, int32_t nr, int32_t nd,
+                        int32_t max_det, const int32_t* d_det_count, const int32_t* d_det_range_idx,
+                        const int32_t* d_det_doppler_idx, const float* d_det_power, const float* d_det_noise,
+                        const fmcw_targets* d_out, int32_t* d_det_label, void* stream);
+
+/* Host pointers: staged, sharded over the context's devices and chunked as fmcw_cfar is
+ * (bit-identical shards); returns when the outputs are on the host. */
+int fmcw_cluster(fmcw_ctx* ctx, const fmcw_cluster_params* q, int64_t F, int32_t nr, int32_t nd, int32_t max_det,
+                 const int32_t* det_count, const int32_t* det_range_idx, const int32_t* det_doppler_idx,
+                 const float* det_power, const float* det_noise, const fmcw_targets* out, int32_t* det_label);
 
 /* ---------------------------------------------------------------------------
  * spectrogram.png, replacing radar_processing.m:331-348:

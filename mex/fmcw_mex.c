@@ -34,6 +34,14 @@
  *                                        ridx(1, :) of 'process', or absent / empty for the fixed gate; dt is
  *                                        Nd x F, rt Nr x F (in dB when Q.flags has FMCW_SIG_DB), the maxima
  *                                        are those of the linear maps
+ *   [tcnt, cells, pk_ridx, pk_didx, ext_r, ext_d, pk_power, pk_noise, power, range, doppler, label] =
+ *       fmcw_mex('cluster', Q, cnt, ridx, didx, power, noise, nr, nd)  -> fmcw_cluster: the detection lists of
+ *                                        'cfar' grouped into targets (beyond the reference, whose range_speed of
+ *                                        :241-252 holds one range and one speed per target); Q: a struct with the
+ *                                        fields of fmcw_cluster_params; cnt 1 x F, ridx ... noise max_det x F as
+ *                                        'cfar' returns them (noise may be []); tcnt is 1 x F, label max_det x F,
+ *                                        the others max_tgt x F; range and doppler are the 1-based power-weighted
+ *                                        centroids.  Outputs that are not asked for are not computed.
  *   fmcw_mex('close')                                             -> fmcw_ctx_destroy
  *
  * P is a struct with the fields of fmcw_params (nts, pn, nr, nd, max_targets,
@@ -298,6 +306,51 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                    mxGetSingles(plhs[1]), &dmx, &rmx));
     plhs[2] = mxCreateDoubleScalar((double)dmx);
     plhs[3] = mxCreateDoubleScalar((double)rmx);
+    return;
+  }
+  if (!strcmp(cmd, "cluster")) {            /* [tcnt, cells, ...] = fmcw_mex('cluster', Q, cnt, ridx, didx, power, noise, nr, nd) */
+    if (nrhs != 9) mexErrMsgIdAndTxt("fmcw:arg", "cluster: Q, cnt, ridx, didx, power, noise, nr, nd");
+    const mxArray* s = prhs[1];
+    if (!mxIsStruct(s)) mexErrMsgIdAndTxt("fmcw:arg", "Q must be a struct");
+    fmcw_cluster_params q;
+    q.link_r = (int32_t)field(s, "link_r");
+    q.link_d = (int32_t)field(s, "link_d");
+    q.min_cells = (int32_t)field(s, "min_cells");
+    q.max_tgt = (int32_t)field(s, "max_tgt");
+    q.flags = (int32_t)field(s, "flags");
+    const int32_t nr = (int32_t)mxGetScalar(prhs[7]), nd = (int32_t)mxGetScalar(prhs[8]);
+    if (!mxIsInt32(prhs[2]) || !mxIsInt32(prhs[3]) || !mxIsInt32(prhs[4]))
+      mexErrMsgIdAndTxt("fmcw:arg", "cnt, ridx and didx must be int32");
+    const int64_t F = (int64_t)mxGetNumberOfElements(prhs[2]);
+    const mwSize K = mxGetM(prhs[3]);
+    check(fmcw_cluster_check(&q, nr, nd, (int32_t)K));   /* before max_tgt sizes the outputs */
+    const mwSize n = K * (mwSize)F, M = (mwSize)q.max_tgt;
+    if (mxGetNumberOfElements(prhs[3]) != n || mxGetNumberOfElements(prhs[4]) != n)
+      mexErrMsgIdAndTxt("fmcw:arg", "ridx and didx must be max_det x F");
+    const float* power = single_real(prhs[5], n, "power");
+    const float* noise = mxGetNumberOfElements(prhs[6]) > 0 ? single_real(prhs[6], n, "noise") : NULL;
+    /* outputs past nlhs do not exist: their pointers stay NULL and the library leaves them out */
+    const int want = nlhs > 1 ? nlhs : 1;
+    void* o[12] = {0};
+    for (int i = 0; i < 12 && i < want; ++i) {
+      const int is_f = i >= 6 && i <= 10;
+      plhs[i] = mxCreateNumericMatrix(i == 0 ? 1 : i == 11 ? K : M, (mwSize)F, is_f ? mxSINGLE_CLASS : mxINT32_CLASS, mxREAL);
+      o[i] = is_f ? (void*)mxGetSingles(plhs[i]) : (void*)mxGetInt32s(plhs[i]);
+    }
+    fmcw_targets t;
+    t.tgt_count = (int32_t*)o[0];
+    t.cells = (int32_t*)o[1];
+    t.peak_range_idx = (int32_t*)o[2];
+    t.peak_doppler_idx = (int32_t*)o[3];
+    t.extent_r = (int32_t*)o[4];
+    t.extent_d = (int32_t*)o[5];
+    t.peak_power = (float*)o[6];
+    t.peak_noise = (float*)o[7];
+    t.power = (float*)o[8];
+    t.range = (float*)o[9];
+    t.doppler = (float*)o[10];
+    check(fmcw_cluster(g_ctx, &q, F, nr, nd, (int32_t)K, mxGetInt32s(prhs[2]), mxGetInt32s(prhs[3]), mxGetInt32s(prhs[4]),
+                       power, noise, &t, (int32_t*)o[11]));
     return;
   }
   mexErrMsgIdAndTxt("fmcw:arg", "unknown command '%s'", cmd);
