@@ -20,7 +20,7 @@ FMCW_PIPE_AUTO, FMCW_PIPE_STREAMS, FMCW_PIPE_ONEPASS, FMCW_PIPE_XCD = 0, 1, 3, 4
 ABI_VERSION = 4
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_HIP", -3: "E_OOM", -4: "E_STATE", -5: "E_DATA"}
 STAGES = ("range", "doppler", "detect", "compact", "stft_power", "stft_db", "range_only", "range_doppler", "onepass",
-          "render", "cfar", "cluster")
+          "render", "cfar", "cluster", "track")
 FMCW_CFAR_LOCAL_MAX = 1
 FMCW_SIG_DB = 1
 
@@ -72,6 +72,23 @@ class Targets(ct.Structure):
 
 TARGET_INT_KEYS = ("cells", "peak_range_idx", "peak_doppler_idx", "extent_r", "extent_d")
 TARGET_FLOAT_KEYS = ("peak_power", "peak_noise", "power", "range", "doppler")
+
+
+class TrackParams(ct.Structure):
+    """fmcw_track_params (include/fmcw.h)."""
+    _fields_ = [("gate_r", ct.c_float), ("gate_d", ct.c_float), ("alpha_r", ct.c_float), ("alpha_d", ct.c_float),
+                ("beta_r", ct.c_float), ("confirm_hits", ct.c_int32), ("max_coast", ct.c_int32),
+                ("max_trk", ct.c_int32), ("flags", ct.c_int32)]
+
+
+class Tracks(ct.Structure):
+    """fmcw_tracks (include/fmcw.h): output pointers, [S*F][max_trk] each but trk_count [S*F]."""
+    _fields_ = [(k, ct.c_void_p) for k in ("trk_count", "trk_id", "trk_status", "trk_age", "trk_misses", "trk_range",
+                                           "trk_range_rate", "trk_doppler", "trk_power")]
+
+
+TRACK_INT_KEYS = ("trk_id", "trk_status", "trk_age", "trk_misses")
+TRACK_FLOAT_KEYS = ("trk_range", "trk_range_rate", "trk_doppler", "trk_power")
 
 
 class JsonField(ct.Structure):
@@ -135,6 +152,12 @@ SIGNATURES = {
                                        ct.POINTER(Targets), _P, _P]),
     "fmcw_cluster": (ct.c_int, [_P, ct.POINTER(ClusterParams), _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P,
                                 ct.POINTER(Targets), _P]),
+    "fmcw_track_check": (ct.c_int, [ct.POINTER(TrackParams), _I32, _I32, _I32]),
+    "fmcw_track_state_bytes": (_I32, [_I32]),
+    "fmcw_track_device": (ct.c_int, [_P, ct.POINTER(TrackParams), _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P,
+                                     ct.POINTER(Tracks), _P, _P]),
+    "fmcw_track": (ct.c_int, [_P, ct.POINTER(TrackParams), _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P,
+                              ct.POINTER(Tracks), _P]),
     "fmcw_json_write": (ct.c_int, [ct.c_char_p, ct.POINTER(JsonField), _I32, _I32, _I32, ct.POINTER(_I64)]),
     "fmcw_stft_png": (ct.c_int, [_P, _P, _I64, _P, _I32, _I32, _I32, _D, _I32, _P, _P, _P, ct.c_char_p, _I32, _I32,
                                  ct.POINTER(_I64)]),

@@ -177,7 +177,7 @@ void shard(int64_t total, int g, int world, int64_t& f0, int64_t& n) {
   n = base + (g < rem ? 1 : 0);
 }
 
-constexpr int kStages = 12;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar, 11 cluster
+constexpr int kStages = 13;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar, 11 cluster, 12 track
 
 }  // namespace
 
@@ -330,6 +330,8 @@ struct fmcw_ctx {
   DevBuf sg_in, sg_ctr, sg_out;
   // fmcw_cluster (host pointers): the chunk's detection lists and the per-frame outputs on the device
   DevBuf cl_in, cl_out;
+  // fmcw_track (host pointers): the chunk's target rows, the chunk's outputs and the sequences' state on the device
+  DevBuf tk_in, tk_out, tk_state;
   int64_t chunk_frames = 0;
   int64_t last_coarse_tiles = -1;     // tiles the last coarse-to-fine max(P) evaluated in full (diagnostics)
   int pipe_mode = FMCW_PIPE_AUTO;
@@ -2534,6 +2536,173 @@ int fmcw_cluster(fmcw_ctx* c, const fmcw_cluster_params* q, int64_t F, int32_t n
     t.doppler = out->doppler ? out->doppler + f0 * M : nullptr;
     return cluster_host_one(d, q, n, nr, nd, max_det, count + f0, ridx + f0 * K, didx + f0 * K, power + f0 * K,
                             noise ? noise + f0 * K : nullptr, t, label ? label + f0 * K : nullptr);
+  });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Tracks from the per-frame targets (kernels_track.hip)
+// ---------------------------------------------------------------------------
+static int track_check_impl(const fmcw_track_params* q, int32_t nr, int32_t nd, int32_t max_tgt) {
+  if (!q) return fail(FMCW_E_ARG, "track params is NULL");
+  if (nr < 16 || nr > 2048 || (nr & (nr - 1))) return fail(FMCW_E_ARG, "track: nr must be a power of two in [16, 2048]");
+  if (nd < 4 || nd > 1024 || (nd & (nd - 1))) return fail(FMCW_E_ARG, "track: nd must be a power of two in [4, 1024]");
+  if (max_tgt < 1 || max_tgt > fmcw::kTrackMax) return fail(FMCW_E_ARG, "track: max_tgt must be in [1, 64]");
+  if (!(std::isfinite(q->gate_r) && q->gate_r > 0.f)) return fail(FMCW_E_ARG, "track: gate_r must be finite and > 0");
+  if (!(std::isfinite(q->gate_d) && q->gate_d > 0.f)) return fail(FMCW_E_ARG, "track: gate_d must be finite and > 0");
+  if (!(q->gate_d < (float)(nd / 2))) return fail(FMCW_E_ARG, "track: gate_d must be below nd/2");
+  if (!(q->alpha_r > 0.f && q->alpha_r <= 1.f)) return fail(FMCW_E_ARG, "track: alpha_r must be in (0, 1]");
+  if (!(q->alpha_d > 0.f && q->alpha_d <= 1.f)) return fail(FMCW_E_ARG, "track: alpha_d must be in (0, 1]");
+  if (!(q->beta_r >= 0.f && q->beta_r <= 1.f)) return fail(FMCW_E_ARG, "track: beta_r must be in [0, 1]");
+  if (q->confirm_hits < 1 || q->confirm_hits > 255) return fail(FMCW_E_ARG, "track: confirm_hits must be in [1, 255]");
+  if (q->max_coast < 0 || q->max_coast > 255) return fail(FMCW_E_ARG, "track: max_coast must be in [0, 255]");
+  if (q->max_trk < 1 || q->max_trk > fmcw::kTrackMax) return fail(FMCW_E_ARG, "track: max_trk must be in [1, 64]");
+  if (q->flags != 0) return fail(FMCW_E_ARG, "track: unknown flag bits");
+  return FMCW_OK;
+}
+
+// rows [f0, f0 + nf) of every one of S sequences, between a host array of F rows per sequence and a
+// dense device array of nf rows per sequence
+static int track_rows(void* dev, void* host, int64_t S, int64_t F, int64_t f0, int64_t nf, size_t rowbytes, bool to_device,
+                      hipStream_t s) {
+  char* const h = static_cast<char*>(host) + (size_t)f0 * rowbytes;
+  const hipMemcpyKind kind = to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+  if (nf == F || S == 1) {
+    if (to_device) HIPCHK(hipMemcpyAsync(dev, h, (size_t)S * nf * rowbytes, kind, s));
+    else HIPCHK(hipMemcpyAsync(h, dev, (size_t)S * nf * rowbytes, kind, s));
+    return FMCW_OK;
+  }
+  const size_t hp = (size_t)F * rowbytes, dp = (size_t)nf * rowbytes;
+  if (to_device) HIPCHK(hipMemcpy2DAsync(dev, dp, h, hp, dp, (size_t)S, kind, s));
+  else HIPCHK(hipMemcpy2DAsync(h, hp, dev, dp, dp, (size_t)S, kind, s));
+  return FMCW_OK;
+}
+
+static int track_host_one(fmcw_ctx* c, const fmcw_track_params* q, int64_t S, int64_t F, int32_t nr, int32_t nd, int32_t M,
+                          const int32_t* count, const float* range, const float* doppler, const float* power, void* state,
+                          const fmcw_tracks& out, int32_t* tgt_track) {
+  CHK(set_device(c));
+  hipStream_t s = c->stream;
+  const int T = q->max_trk;
+  const size_t sbytes = (size_t)fmcw::track_state_words(T) * 4;
+  const size_t frow = (size_t)M * 4, trow = (size_t)T * 4;
+  // frames per chunk: a chunk holds that many frames of every sequence of the shard
+  const int64_t Fc = host_chunk((size_t)S * (4 + 3 * frow), F);
+  Arena in, ou;
+  const size_t i_count = in.add((size_t)S * Fc * 4), i_r = in.add((size_t)S * Fc * frow), i_d = in.add((size_t)S * Fc * frow),
+               i_p = in.add((size_t)S * Fc * frow);
+  size_t o_off[10];
+  o_off[0] = ou.add((size_t)S * Fc * 4);
+  for (int i = 1; i < 9; ++i) o_off[i] = ou.add((size_t)S * Fc * trow);
+  o_off[9] = ou.add((size_t)S * Fc * frow);
+  CHK(c->tk_in.ensure(in.off));
+  CHK(c->tk_out.ensure(ou.off));
+  CHK(c->tk_state.ensure((size_t)S * sbytes));
+  char* const di = c->tk_in.as<char>();
+  char* const o = c->tk_out.as<char>();
+  if (state) HIPCHK(hipMemcpyAsync(c->tk_state.p, state, (size_t)S * sbytes, hipMemcpyHostToDevice, s));
+  else HIPCHK(hipMemsetAsync(c->tk_state.p, 0, (size_t)S * sbytes, s));
+  void* const host[10] = {out.trk_count, out.trk_id, out.trk_status, out.trk_age, out.trk_misses,
+                          out.trk_range, out.trk_range_rate, out.trk_doppler, out.trk_power, tgt_track};
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    const int64_t nf = std::min(Fc, F - f0);
+    CHK(track_rows(di + i_count, const_cast<int32_t*>(count), S, F, f0, nf, 4, true, s));
+    CHK(track_rows(di + i_r, const_cast<float*>(range), S, F, f0, nf, frow, true, s));
+    CHK(track_rows(di + i_d, const_cast<float*>(doppler), S, F, f0, nf, frow, true, s));
+    CHK(track_rows(di + i_p, const_cast<float*>(power), S, F, f0, nf, frow, true, s));
+    fmcw_tracks d{};
+    d.trk_count = reinterpret_cast<int32_t*>(o + o_off[0]);
+    int32_t** const ip[4] = {&d.trk_id, &d.trk_status, &d.trk_age, &d.trk_misses};
+    float** const fp[4] = {&d.trk_range, &d.trk_range_rate, &d.trk_doppler, &d.trk_power};
+    for (int i = 0; i < 4; ++i) {
+      *ip[i] = host[1 + i] ? reinterpret_cast<int32_t*>(o + o_off[1 + i]) : nullptr;
+      *fp[i] = host[5 + i] ? reinterpret_cast<float*>(o + o_off[5 + i]) : nullptr;
+    }
+    CHK(fmcw_track_device(c, q, S, nf, nr, nd, M, reinterpret_cast<int32_t*>(di + i_count),
+                          reinterpret_cast<float*>(di + i_r), reinterpret_cast<float*>(di + i_d),
+                          reinterpret_cast<float*>(di + i_p), c->tk_state.p, &d,
+                          tgt_track ? reinterpret_cast<int32_t*>(o + o_off[9]) : nullptr, s));
+    for (int i = 0; i < 10; ++i)
+      if (host[i]) CHK(track_rows(o + o_off[i], host[i], S, F, f0, nf, i == 0 ? 4 : i == 9 ? frow : trow, false, s));
+    HIPCHK(hipStreamSynchronize(s));           // the chunk buffers are reused by the next chunk
+  }
+  if (state) HIPCHK(hipMemcpyAsync(state, c->tk_state.p, (size_t)S * sbytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return FMCW_OK;
+}
+
+extern "C" {
+
+int fmcw_track_check(const fmcw_track_params* q, int32_t nr, int32_t nd, int32_t max_tgt) {
+  return track_check_impl(q, nr, nd, max_tgt);
+}
+
+int32_t fmcw_track_state_bytes(int32_t max_trk) {
+  if (max_trk < 1 || max_trk > fmcw::kTrackMax) return fail(FMCW_E_ARG, "track: max_trk must be in [1, 64]");
+  return fmcw::track_state_words(max_trk) * 4;
+}
+
+int fmcw_track_device(fmcw_ctx* c, const fmcw_track_params* q, int64_t S, int64_t F, int32_t nr, int32_t nd, int32_t max_tgt,
+                      const int32_t* d_count, const float* d_range, const float* d_doppler, const float* d_power,
+                      void* d_state, const fmcw_tracks* d_out, int32_t* d_tgt_track, void* stream) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(track_check_impl(q, nr, nd, max_tgt));
+  if (F < 0 || S < 0) return fail(FMCW_E_ARG, "S < 0 or F < 0");
+  if (S > 0x7fffffffLL || F > ((int64_t)1 << 40) / std::max<int64_t>(S, 1))
+    return fail(FMCW_E_ARG, "track: S must be below 2^31 and S * F at most 2^40");
+  if (F == 0 || S == 0) return FMCW_OK;
+  if (!d_count || !d_range || !d_doppler || !d_power || !d_state || !d_out || !d_out->trk_count)
+    return fail(FMCW_E_ARG, "required pointer is NULL");
+  CHK(set_device(c));
+  hipStream_t s = pick(c, stream);
+  fmcw::TrackArgs a{};
+  a.S = S; a.F = F; a.NR = nr; a.ND = nd; a.M = max_tgt; a.T = q->max_trk;
+  a.wr = (float)(1.0 / ((double)q->gate_r * q->gate_r));
+  a.wd = (float)(1.0 / ((double)q->gate_d * q->gate_d));
+  a.alpha_r = q->alpha_r; a.alpha_d = q->alpha_d; a.beta_r = q->beta_r;
+  a.confirm_hits = q->confirm_hits; a.max_coast = q->max_coast;
+  a.tgt_count = d_count; a.range = d_range; a.doppler = d_doppler; a.power = d_power;
+  a.state = static_cast<uint32_t*>(d_state);
+  a.trk_count = d_out->trk_count;
+  a.trk_id = d_out->trk_id; a.trk_status = d_out->trk_status; a.trk_age = d_out->trk_age; a.trk_misses = d_out->trk_misses;
+  a.trk_range = d_out->trk_range; a.trk_rate = d_out->trk_range_rate; a.trk_doppler = d_out->trk_doppler;
+  a.trk_power = d_out->trk_power;
+  a.tgt_track = d_tgt_track;
+  StageTimer tm(c, 12, s);
+  HIPCHK(fmcw::launch_track(a, s));
+  tm.done();
+  return FMCW_OK;
+}
+
+int fmcw_track(fmcw_ctx* c, const fmcw_track_params* q, int64_t S, int64_t F, int32_t nr, int32_t nd, int32_t max_tgt,
+               const int32_t* count, const float* range, const float* doppler, const float* power, void* state,
+               const fmcw_tracks* out, int32_t* tgt_track) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(track_check_impl(q, nr, nd, max_tgt));
+  if (F < 0 || S < 0) return fail(FMCW_E_ARG, "S < 0 or F < 0");
+  if (S > 0x7fffffffLL || F > ((int64_t)1 << 40) / std::max<int64_t>(S, 1))
+    return fail(FMCW_E_ARG, "track: S must be below 2^31 and S * F at most 2^40");
+  if (F == 0 || S == 0) return FMCW_OK;
+  if (!count || !range || !doppler || !power || !out || !out->trk_count) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const int64_t M = max_tgt, T = q->max_trk;
+  const size_t sbytes = (size_t)fmcw::track_state_words(q->max_trk) * 4;
+  // the frames of a sequence depend on each other, the sequences do not: contiguous shards of sequences
+  return over_devices(c, S, [&](fmcw_ctx* d, int, int64_t s0, int64_t n) {
+    const int64_t r0 = s0 * F;
+    fmcw_tracks t{};
+    t.trk_count = out->trk_count + r0;
+    t.trk_id = out->trk_id ? out->trk_id + r0 * T : nullptr;
+    t.trk_status = out->trk_status ? out->trk_status + r0 * T : nullptr;
+    t.trk_age = out->trk_age ? out->trk_age + r0 * T : nullptr;
+    t.trk_misses = out->trk_misses ? out->trk_misses + r0 * T : nullptr;
+    t.trk_range = out->trk_range ? out->trk_range + r0 * T : nullptr;
+    t.trk_range_rate = out->trk_range_rate ? out->trk_range_rate + r0 * T : nullptr;
+    t.trk_doppler = out->trk_doppler ? out->trk_doppler + r0 * T : nullptr;
+    t.trk_power = out->trk_power ? out->trk_power + r0 * T : nullptr;
+    return track_host_one(d, q, n, F, nr, nd, max_tgt, count + r0, range + r0 * M, doppler + r0 * M, power + r0 * M,
+                          state ? static_cast<char*>(state) + (size_t)s0 * sbytes : nullptr, t,
+                          tgt_track ? tgt_track + r0 * M : nullptr);
   });
 }
 

@@ -363,6 +363,32 @@ struct ClusterArgs {
 };
 hipError_t launch_cluster(const ClusterArgs& a, hipStream_t s);
 
+// Tracking of the per-frame targets across frames (kernels_track.hip): k_track
+// One sequence's state block: kTrackFields arrays of T = max_trk 32-bit words (id, status, hits,
+// misses, age as int32; r, v, d, power as float32), then the id counter, padded to 16 bytes.
+constexpr int kTrackFields = 9;
+constexpr int kTrackMax = 64;          // max_trk and max_tgt at most: a slot / a measurement per lane
+constexpr int track_state_words(int max_trk) { return (kTrackFields * max_trk + 1 + 3) & ~3; }
+struct TrackArgs {
+  int64_t S, F;                    // sequences, frames per sequence
+  int NR, ND;
+  int M, T;                        // max_tgt, max_trk
+  float wr, wd;                    // 1 / gate_r^2, 1 / gate_d^2
+  float alpha_r, alpha_d, beta_r;
+  int confirm_hits, max_coast;
+  const int32_t* tgt_count;        // [S*F]
+  const float* range;              // [S*F][M]
+  const float* doppler;            // [S*F][M]
+  const float* power;              // [S*F][M]
+  uint32_t* state;                 // [S][track_state_words(T)]
+  int32_t* trk_count;              // [S*F]
+  // [S*F][T] each, any may be nullptr
+  int32_t* trk_id; int32_t* trk_status; int32_t* trk_age; int32_t* trk_misses;
+  float* trk_range; float* trk_rate; float* trk_doppler; float* trk_power;
+  int32_t* tgt_track;              // [S*F][M] or nullptr
+};
+hipError_t launch_track(const TrackArgs& a, hipStream_t s);
+
 bool range_size_supported(int nr);
 bool doppler_size_supported(int nd);
 

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import FMCW_C32H, FMCW_C64, STAGES, FmcwError, check
-from .params import CfarConfig, ClusterConfig, FmcwConfig, SigConfig
+from .params import CfarConfig, ClusterConfig, FmcwConfig, SigConfig, TrackConfig
 
 
 def _ptr(a) -> ct.c_void_p:
@@ -439,6 +439,91 @@ class Engine:
                                  d_cube=d_cube, probe_column=probe_column, stream=stream)
         self.cluster_device(q_cluster, F, cfg.nr, cfg.nd, q_cfar.max_det, cfar_outs, tgt_outs,
                             d_det_label=d_det_label, stream=stream)
+
+    # ---- tracks from the per-frame targets (include/fmcw.h, fmcw_track_params) ----------------
+    def track_state_bytes(self, max_trk: int) -> int:
+        """fmcw_track_state_bytes: the bytes of one sequence's state block."""
+        n = self.lib.fmcw_track_state_bytes(int(max_trk))
+        if n < 0:
+            check(n)
+        return n
+
+    def track(self, tgts: dict, q: TrackConfig, nr: int, nd: int, n_seq: int = 1, state: np.ndarray | None = None) -> dict:
+        """Tracks over the targets `tgts` (the dict Engine.cluster returns, or any dict with tgt_count
+        [S*F] and range, doppler, peak_power [S*F][max_tgt]): n_seq = S independent sequences of F
+        consecutive frames each, sequence s in the rows s*F .. s*F + F - 1.  Host arrays; the sequences
+        are sharded over the context's devices.  state: None for fresh sequences, or the uint8
+        [S][track_state_bytes(max_trk)] array an earlier call returned, to carry the sequences on.
+        Returns trk_count [S*F]; trk_id, trk_status, trk_age, trk_misses (int32) and trk_range,
+        trk_range_rate, trk_doppler, trk_power (float32), each [S*F][max_trk] and 0 for a free slot;
+        tgt_track [S*F][max_tgt]; `state` after the last frame; and, once set_taps has given the
+        geometry's scales, range_m, speed_mps and range_rate_mps_per_frame (NaN for free slots)."""
+        cnt = np.ascontiguousarray(tgts["tgt_count"], np.int32)
+        zr = np.ascontiguousarray(tgts["range"], np.float32)
+        zd = np.ascontiguousarray(tgts["doppler"], np.float32)
+        zp = np.ascontiguousarray(tgts["peak_power"], np.float32)
+        rows, S = cnt.shape[0], int(n_seq)
+        if cnt.ndim != 1 or zr.ndim != 2 or zr.shape[0] != rows or zd.shape != zr.shape or zp.shape != zr.shape:
+            raise ValueError("the targets must be [S*F][max_tgt], tgt_count [S*F]")
+        if S < 1 or rows % S:
+            raise ValueError("n_seq must divide the number of rows")
+        F, M, T = rows // S, zr.shape[1], int(q.max_trk)
+        sb = self.track_state_bytes(T)
+        if state is None:
+            st = np.zeros((S, sb), np.uint8)
+        else:
+            st = np.array(state, dtype=np.uint8, order="C", copy=True)
+            if st.shape != (S, sb):
+                raise ValueError(f"state must be uint8 [{S}][{sb}]")
+        out = dict(trk_count=np.zeros(rows, np.int32))
+        for k in _lib.TRACK_INT_KEYS:
+            out[k] = np.zeros((rows, T), np.int32)
+        for k in _lib.TRACK_FLOAT_KEYS:
+            out[k] = np.zeros((rows, T), np.float32)
+        out["tgt_track"] = np.zeros((rows, M), np.int32)
+        qa = q.abi()
+        t = _lib.Tracks(*[_ptr(out[k]) for k, _ in _lib.Tracks._fields_])
+        check(self.lib.fmcw_track(self.h, ct.byref(qa), S, F, int(nr), int(nd), M, _ptr(cnt), _ptr(zr), _ptr(zd),
+                                  _ptr(zp), _ptr(st), ct.byref(t), _ptr(out["tgt_track"])))
+        out["state"] = st
+        if self.cfg is not None and (self.cfg.nr, self.cfg.nd) == (int(nr), int(nd)):
+            used = out["trk_status"] > 0
+            out["range_m"] = np.where(used, self.cfg.range_m(out["trk_range"]), np.nan)
+            out["speed_mps"] = np.where(used, self.cfg.speed(out["trk_doppler"]), np.nan)
+            out["range_rate_mps_per_frame"] = np.where(
+                used, out["trk_range_rate"].astype(np.float64) * self.cfg.dist_per_bin, np.nan)
+        return out
+
+    def track_device(self, q: TrackConfig, S: int, F: int, nr: int, nd: int, max_tgt: int, tgts: dict, d_state,
+                     outs: dict, d_tgt_track=None, stream=None) -> None:
+        """fmcw_track_device: tgts holds the device buffers fmcw_cluster_device wrote (tgt_count [S*F],
+        range, doppler, peak_power [S*F][max_tgt]); d_state the uint8 [S][track_state_bytes(max_trk)]
+        state, read and rewritten in place (zeros: fresh sequences); outs the device buffers trk_count
+        [S*F] int32 and any of trk_id, trk_status, trk_age, trk_misses (int32), trk_range,
+        trk_range_rate, trk_doppler, trk_power (float32), [S*F][max_trk] each (missing or None: not
+        written); d_tgt_track [S*F][max_tgt] int32 or None.  q: a TrackConfig, or the C struct
+        _lib.TrackParams itself.  Asynchronous on `stream`."""
+        qa = q.abi() if hasattr(q, "abi") else q
+        t = _lib.Tracks(*[_ptr(outs.get(k)) for k, _ in _lib.Tracks._fields_])
+        with _sided(stream) as hs:
+            check(self.lib.fmcw_track_device(self.h, ct.byref(qa), int(S), int(F), int(nr), int(nd), int(max_tgt),
+                                             _ptr(tgts["tgt_count"]), _ptr(tgts["range"]), _ptr(tgts["doppler"]),
+                                             _ptr(tgts["peak_power"]), _ptr(d_state), ct.byref(t), _ptr(d_tgt_track),
+                                             hs))
+
+    def process_tracks_device(self, d_iq, F: int, in_dtype: int, outs: dict, q_cfar: CfarConfig, d_rd, cfar_outs: dict,
+                              q_cluster: ClusterConfig, tgt_outs: dict, q_track: TrackConfig, d_state, trk_outs: dict,
+                              d_tgt_track=None, d_det_label=None, out_dtype: int = FMCW_C64, d_mask=None, d_cube=None,
+                              probe_column: int = 0, stream=None) -> None:
+        """IQ in, tracks out, on one stream with no host round trip: process_targets_device (targets
+        to tgt_outs, which must hold range, doppler and peak_power), then track_device over the F
+        frames as one sequence, carried on from d_state."""
+        cfg = self._need()
+        self.process_targets_device(d_iq, F, in_dtype, outs, q_cfar, d_rd, cfar_outs, q_cluster, tgt_outs,
+                                    d_det_label=d_det_label, out_dtype=out_dtype, d_mask=d_mask, d_cube=d_cube,
+                                    probe_column=probe_column, stream=stream)
+        self.track_device(q_track, 1, F, cfg.nr, cfg.nd, q_cluster.max_tgt, tgt_outs, d_state, trk_outs,
+                          d_tgt_track=d_tgt_track, stream=stream)
 
     # ---- timing -----------------------------------------------------------------
     def timing(self, level: int) -> None:

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import windows
-from ._lib import FMCW_CFAR_LOCAL_MAX, FMCW_SIG_DB, CfarParams, ClusterParams, Params, SigParams
+from ._lib import FMCW_CFAR_LOCAL_MAX, FMCW_SIG_DB, CfarParams, ClusterParams, Params, SigParams, TrackParams
 
 C0 = 3e8  # radar_processing.m:67
 
@@ -249,6 +249,68 @@ class ClusterConfig:
         default): 8-connectivity, single-cell clusters (isolated false alarms) dropped."""
         q = cls(link_r=int(link[0]), link_d=int(link[1]), min_cells=int(min_cells), max_tgt=int(max_tgt))
         q.validate(cfg.nr, cfg.nd, int(max_det))
+        return q
+
+
+@dataclass
+class TrackConfig:
+    """fmcw_track_params (include/fmcw.h): tracks the targets of fmcw_cluster across frames.  A
+    measurement is associated with a track inside the gate (er / gate_r)^2 + (x / gate_d)^2 <= 1 (bins,
+    Doppler circular); alpha_r / beta_r filter the range and the range rate, alpha_d the Doppler; a
+    track is confirmed at confirm_hits hits and coasts through at most max_coast missed frames."""
+    gate_r: float = 4.0
+    gate_d: float = 4.0
+    alpha_r: float = 0.5
+    alpha_d: float = 0.5
+    beta_r: float = 0.25
+    confirm_hits: int = 3
+    max_coast: int = 3
+    max_trk: int = 16
+
+    def abi(self) -> TrackParams:
+        return TrackParams(self.gate_r, self.gate_d, self.alpha_r, self.alpha_d, self.beta_r, self.confirm_hits,
+                           self.max_coast, self.max_trk, 0)
+
+    def validate(self, nr: int, nd: int, max_tgt: int) -> None:
+        """The rules of fmcw_track_check, on the float32 values the C struct carries; ValueError
+        naming the first one violated."""
+        f = np.float32
+        if nr < 16 or nr > 2048 or nr & (nr - 1):
+            raise ValueError("track: nr must be a power of two in [16, 2048]")
+        if nd < 4 or nd > 1024 or nd & (nd - 1):
+            raise ValueError("track: nd must be a power of two in [4, 1024]")
+        if not 1 <= max_tgt <= 64:
+            raise ValueError("track: max_tgt must be in [1, 64]")
+        with np.errstate(over="ignore"):
+            gr, gd, ar, ad, br = (f(x) for x in (self.gate_r, self.gate_d, self.alpha_r, self.alpha_d, self.beta_r))
+        if not (np.isfinite(gr) and gr > 0):
+            raise ValueError("track: gate_r must be finite and > 0")
+        if not (np.isfinite(gd) and gd > 0):
+            raise ValueError("track: gate_d must be finite and > 0")
+        if not gd < f(nd // 2):
+            raise ValueError("track: gate_d must be below nd/2")
+        if not 0 < ar <= 1:
+            raise ValueError("track: alpha_r must be in (0, 1]")
+        if not 0 < ad <= 1:
+            raise ValueError("track: alpha_d must be in (0, 1]")
+        if not 0 <= br <= 1:
+            raise ValueError("track: beta_r must be in [0, 1]")
+        if not 1 <= self.confirm_hits <= 255:
+            raise ValueError("track: confirm_hits must be in [1, 255]")
+        if not 0 <= self.max_coast <= 255:
+            raise ValueError("track: max_coast must be in [0, 255]")
+        if not 1 <= self.max_trk <= 64:
+            raise ValueError("track: max_trk must be in [1, 64]")
+
+    @classmethod
+    def for_config(cls, cfg: "FmcwConfig", gate=(4.0, 4.0), alpha=(0.5, 0.5), beta_r: float = 0.25,
+                   confirm_hits: int = 3, max_coast: int = 3, max_trk: int = 16, max_tgt: int = 16) -> "TrackConfig":
+        """The tracker for cfg's RD map and target lists of max_tgt entries (ClusterConfig.for_config's
+        default); the Doppler gate is cut to stay below nd/2 on a short ring."""
+        gd = min(float(gate[1]), cfg.nd / 2 - 0.5)
+        q = cls(gate_r=float(gate[0]), gate_d=gd, alpha_r=float(alpha[0]), alpha_d=float(alpha[1]),
+                beta_r=float(beta_r), confirm_hits=int(confirm_hits), max_coast=int(max_coast), max_trk=int(max_trk))
+        q.validate(cfg.nr, cfg.nd, int(max_tgt))
         return q
 
 

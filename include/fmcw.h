@@ -46,7 +46,10 @@ extern "C" {
  *    fmcw_sig), added within ABI 4 in the same way
  *    + the clustering entry points (fmcw_cluster_check, fmcw_cluster_device, fmcw_cluster), the
  *    structs fmcw_cluster_params / fmcw_targets and timing stage 11, added within ABI 4 in the
- *    same way */
+ *    same way
+ *    + the tracking entry points (fmcw_track_check, fmcw_track_state_bytes, fmcw_track_device,
+ *    fmcw_track), the structs fmcw_track_params / fmcw_tracks and timing stage 12, added within
+ *    ABI 4 in the same way */
 #define FMCW_ABI_VERSION 4
 
 typedef enum fmcw_status {
@@ -273,7 +276,8 @@ int fmcw_synth_device(fmcw_ctx* ctx, const fmcw_params* p, int64_t frame0, int64
  *        6 range_only, 7 range+Doppler span, 8 k_rdx (single-pass schedule,
  *        level 2), 9 render (spectrogram.png), 10 cfar (one pair per k_cfar + k_cfar_gather
  *        launch pair of fmcw_cfar_device), 11 cluster (one pair per k_cluster launch of
- *        fmcw_cluster_device).  fmcw_timing_read synchronises. */
+ *        fmcw_cluster_device), 12 track (one pair per k_track launch of fmcw_track_device).
+ *        fmcw_timing_read synchronises. */
 int fmcw_timing_enable(fmcw_ctx* ctx, int32_t enable);
 int fmcw_timing_read(fmcw_ctx* ctx, int32_t stage, double* total_ms, int64_t* launches);
 int fmcw_timing_reset(fmcw_ctx* ctx);
@@ -525,6 +529,114 @@ int fmcw_cluster_device(fmcw_ctx* ctx, const fmcw_cluster_params* q, int64_t F, 
 int fmcw_cluster(fmcw_ctx* ctx, const fmcw_cluster_params* q, int64_t F, int32_t nr, int32_t nd, int32_t max_det,
                  const int32_t* det_count, const int32_t* det_range_idx, const int32_t* det_doppler_idx,
                  const float* det_power, const float* det_noise, const fmcw_targets* out, int32_t* det_label);
+
+/* ---------------------------------------------------------------------------
+ * Tracks from the per-frame targets: association, alpha-beta filter, ids (added within ABI 4; the
+ * reference's deliverable range_speed, :241-252 / :385-389, is a time series of one range and one
+ * speed per target, which needs to know which target of one frame is which target of the next).
+ * Every index and id is 1-based, 0 means "none".
+ *   Input: what fmcw_cluster* writes, never the RD map or the detection lists.  A call covers S
+ *     independent sequences of F consecutive frames each; frame f of sequence s is row s*F + f of
+ *     tgt_count [S*F] and of range, doppler, peak_power [S*F][max_tgt] (range, doppler: the cluster
+ *     centroids in bins, float32).  n = clamp(tgt_count, 0, max_tgt).  Measurement j < n is valid iff
+ *     range and doppler are finite, 0.5 <= range < nr + 0.5 and 0.5 <= doppler < nd + 0.5; an invalid
+ *     measurement is ignored as if absent.  Measurement values are only compared and copied, never
+ *     used as addresses.
+ *   Parameters: gate_r, gate_d (bins) finite and > 0, gate_d < nd/2; alpha_r, alpha_d in (0, 1];
+ *     beta_r in [0, 1]; confirm_hits in 1..255; max_coast in 0..255; max_trk in 1..64; flags 0;
+ *     nr, nd within CFAR's limits; max_tgt in 1..64.  The host forms
+ *     wr = float(1.0 / ((double)gate_r * gate_r)) and wd likewise.
+ *   State: per sequence max_trk slots -- id, status (0 free, 1 tentative, 2 confirmed), hits,
+ *     misses, age, r, v (bins per frame), d, power -- and an id counter, in
+ *     fmcw_track_state_bytes(max_trk) bytes.  The layout is private, with two guarantees: an
+ *     all-zero block is a fresh sequence, and a freed slot is all zero.  Gains may change between
+ *     calls, max_trk may not.
+ *   One frame step, in float32, every operation rounded on its own in the order written (no fused
+ *   multiply-add):
+ *   1. Predict.  For every live slot k: rp = r + v.  Doppler is not extrapolated.
+ *   2. Cost.  For every pair (live slot k, valid measurement j): er = zr_j - rp_k; x = zd_j - d_k,
+ *      then x -= nd if x >= nd/2, else x += nd if x < -nd/2; c = (er*er)*wr + (x*x)*wd.  The pair is
+ *      admissible iff c <= 1.0f (NaN never is).
+ *   3. Associate (greedy).  The admissible pairs in ascending order of the tuple (tentative slot ?
+ *      1 : 0, bits of c, k, j); a pair is taken iff neither its slot nor its measurement is taken
+ *      yet.  So confirmed tracks choose first, and ties go to the lower slot, then the lower j.
+ *   4. Update.  A slot assigned to measurement j: if its hits are 1 (two-point start) r = zr_j,
+ *      v = er, d = zd_j; otherwise r = rp + alpha_r*er, v = v + beta_r*er, dn = d + alpha_d*x, then
+ *      one conditional dn -= nd if dn >= nd + 0.5 followed by one conditional dn += nd if dn < 0.5,
+ *      d = dn.  In both cases power = zp_j, hits + 1, misses = 0, age + 1, and a tentative slot with
+ *      hits >= confirm_hits becomes confirmed.  A live slot with no measurement: r = rp, misses + 1,
+ *      age + 1; a tentative one is freed at once, a confirmed one when misses > max_coast.  A live
+ *      slot whose r has left [0.5, nr + 0.5) is freed.
+ *   5. Births.  The valid unassigned measurements, in ascending j, take the free slots in ascending
+ *      k (slots freed in step 4 count).  The new slot: id = the sequence's counter pre-incremented
+ *      (first id 1), tentative (confirmed when confirm_hits == 1), hits 1, misses 0, age 1, r = zr_j,
+ *      v = 0, d = zd_j, power = zp_j.  With no slot free the measurement is dropped.
+ *   6. Outputs of the frame, taken after step 5 (fmcw_tracks; [S*F][max_trk] each but trk_count
+ *      [S*F]; any member but trk_count may be NULL): trk_count the number of confirmed slots;
+ *      trk_id, trk_status, trk_age, trk_misses (i32) and trk_range, trk_range_rate, trk_doppler,
+ *      trk_power (f32) the slot values, 0 for a free slot.  A track keeps its slot for life, so a
+ *      column is a trajectory.  tgt_track [S*F][max_tgt] i32 (optional): the id of the track that
+ *      measurement j updated or started, 0 if it was dropped, invalid or unused.
+ *   Results are bit-identical from call to call.  A sequence's results do not depend on S or on
+ *   which other sequences share the call.  F frames in one call equal any split into consecutive
+ *   calls with the state carried, byte for byte, in every output and in the final state block.  For
+ *   any input bytes and any state bytes the call ends and touches nothing out of bounds (a slot
+ *   index is a lane index, n is clamped).
+ *   Measured on one MI355X on the cluster outputs of 4096 frames of 1024 x 256, max_tgt 16, max_trk 16
+ *   (profiles/track_bench.json, 2026-10-20, tree 0e93d61+): a frame step costs 1.3 us at 1.6 targets per
+ *   frame and 2.9 us at 16, alone or with 63 other sequences beside it -- one sequence of 4096 frames
+ *   5.36 / 11.73 ms, 64 sequences of 64 frames 0.090 / 0.190 ms -- beside 8.41 / 10.18 ms for the
+ *   fmcw_cfar_device call and 0.018 / 0.205 ms for the fmcw_cluster_device call of the same run, and
+ *   0.005-0.007 ms for fmcw_copy_device over the bytes the stage reads and writes: a dependency chain
+ *   over frames, bound by latency, not by bytes.
+ * ------------------------------------------------------------------------- */
+typedef struct fmcw_track_params {
+  float   gate_r, gate_d;  /* bins; finite, > 0; gate_d < nd/2 */
+  float   alpha_r, alpha_d;/* (0, 1] */
+  float   beta_r;          /* [0, 1] */
+  int32_t confirm_hits;    /* 1..255 */
+  int32_t max_coast;       /* 0..255 */
+  int32_t max_trk;         /* 1..64 */
+  int32_t flags;           /* 0 */
+} fmcw_track_params;
+
+/* Output pointers, [S*F][max_trk] each but trk_count [S*F]; any member except trk_count may be NULL. */
+typedef struct fmcw_tracks {
+  int32_t* trk_count;
+  int32_t* trk_id;
+  int32_t* trk_status;
+  int32_t* trk_age;
+  int32_t* trk_misses;
+  float*   trk_range;
+  float*   trk_range_rate;
+  float*   trk_doppler;
+  float*   trk_power;
+} fmcw_tracks;
+
+/* Host only, no context.  fmcw_track_check: FMCW_E_ARG (with a message) for any violation of the
+ * constraints.  fmcw_track_state_bytes: the bytes of one sequence's state block (a multiple of 16,
+ * growing with max_trk), or FMCW_E_ARG for a max_trk outside 1..64. */
+int fmcw_track_check(const fmcw_track_params* q, int32_t nr, int32_t nd, int32_t max_tgt);
+int32_t fmcw_track_state_bytes(int32_t max_trk);
+
+/* Device pointers (the members of *d_out are device pointers, the struct itself is read on the host),
+ * asynchronous on `stream`; needs no fmcw_set_taps.  Acts on the context's first device.
+ * d_state [S][fmcw_track_state_bytes(max_trk)], 16-byte aligned, is read and rewritten in place.
+ * F = 0 or S = 0 is a no-op.  FMCW_E_ARG is returned before any launch: the outputs and the state are
+ * then untouched.  d_tgt_track may be NULL. */
+int fmcw_track_device(fmcw_ctx* ctx, const fmcw_track_params* q, int64_t S, int64_t F, int32_t nr, int32_t nd,
+                      int32_t max_tgt, const int32_t* d_tgt_count, const float* d_range, const float* d_doppler,
+                      const float* d_peak_power, void* d_state, const fmcw_tracks* d_out, int32_t* d_tgt_track,
+                      void* stream);
+
+/* Host pointers.  state [S][fmcw_track_state_bytes(max_trk)] is read and rewritten, or NULL: the
+ * sequences start fresh and their state is discarded.  Sequences, never frames, are sharded
+ * contiguously over the context's devices; the frames are staged in chunks with the state kept on the
+ * device between chunks (bit-identical, by the split guarantee above).  Returns when the outputs are
+ * on the host. */
+int fmcw_track(fmcw_ctx* ctx, const fmcw_track_params* q, int64_t S, int64_t F, int32_t nr, int32_t nd,
+               int32_t max_tgt, const int32_t* tgt_count, const float* range, const float* doppler,
+               const float* peak_power, void* state, const fmcw_tracks* out, int32_t* tgt_track);
 
 /* ---------------------------------------------------------------------------
  * spectrogram.png, replacing radar_processing.m:331-348:

@@ -42,6 +42,16 @@
  *                                        'cfar' returns them (noise may be []); tcnt is 1 x F, label max_det x F,
  *                                        the others max_tgt x F; range and doppler are the 1-based power-weighted
  *                                        centroids.  Outputs that are not asked for are not computed.
+ *   [kcnt, id, status, age, misses, range, rate, doppler, power, tgt_track, state] =
+ *       fmcw_mex('track', Q, tcnt, range, doppler, power, nr, nd, nseq[, state])  -> fmcw_track: the targets of
+ *                                        'cluster' tracked across frames (the per-target time series range_speed
+ *                                        of :385-389 needs to know which target is which); Q: a struct with the
+ *                                        fields of fmcw_track_params; tcnt 1 x (nseq*F), range, doppler, power
+ *                                        max_tgt x (nseq*F) as 'cluster' returns them (sequence s in the columns
+ *                                        s*F+1 .. s*F+F); state: int32, fmcw_track_state_bytes(max_trk)/4 x nseq, as
+ *                                        an earlier call returned it, or absent / [] for fresh sequences; kcnt is
+ *                                        1 x (nseq*F), tgt_track max_tgt x (nseq*F), the others max_trk x (nseq*F):
+ *                                        a row is the trajectory of one slot.  Outputs not asked for are not computed.
  *   fmcw_mex('close')                                             -> fmcw_ctx_destroy
  *
  * P is a struct with the fields of fmcw_params (nts, pn, nr, nd, max_targets,
@@ -351,6 +361,64 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     t.doppler = (float*)o[10];
     check(fmcw_cluster(g_ctx, &q, F, nr, nd, (int32_t)K, mxGetInt32s(prhs[2]), mxGetInt32s(prhs[3]), mxGetInt32s(prhs[4]),
                        power, noise, &t, (int32_t*)o[11]));
+    return;
+  }
+  if (!strcmp(cmd, "track")) {              /* [kcnt, id, ...] = fmcw_mex('track', Q, tcnt, range, doppler, power, nr, nd, nseq[, state]) */
+    if (nrhs != 9 && nrhs != 10) mexErrMsgIdAndTxt("fmcw:arg", "track: Q, tcnt, range, doppler, power, nr, nd, nseq[, state]");
+    const mxArray* s = prhs[1];
+    if (!mxIsStruct(s)) mexErrMsgIdAndTxt("fmcw:arg", "Q must be a struct");
+    fmcw_track_params q;
+    q.gate_r = (float)field(s, "gate_r");
+    q.gate_d = (float)field(s, "gate_d");
+    q.alpha_r = (float)field(s, "alpha_r");
+    q.alpha_d = (float)field(s, "alpha_d");
+    q.beta_r = (float)field(s, "beta_r");
+    q.confirm_hits = (int32_t)field(s, "confirm_hits");
+    q.max_coast = (int32_t)field(s, "max_coast");
+    q.max_trk = (int32_t)field(s, "max_trk");
+    q.flags = (int32_t)field(s, "flags");
+    const int32_t nr = (int32_t)mxGetScalar(prhs[6]), nd = (int32_t)mxGetScalar(prhs[7]);
+    const int64_t S = (int64_t)mxGetScalar(prhs[8]);
+    if (!mxIsInt32(prhs[2])) mexErrMsgIdAndTxt("fmcw:arg", "tcnt must be int32");
+    const int64_t rows = (int64_t)mxGetNumberOfElements(prhs[2]);
+    const mwSize M = mxGetM(prhs[3]);
+    check(fmcw_track_check(&q, nr, nd, (int32_t)M));     /* before max_trk sizes the outputs */
+    if (S < 1 || rows % S) mexErrMsgIdAndTxt("fmcw:arg", "nseq must divide the number of frames");
+    const int64_t F = rows / S;
+    const mwSize n = M * (mwSize)rows, T = (mwSize)q.max_trk;
+    const float* range = single_real(prhs[3], n, "range");
+    const float* doppler = single_real(prhs[4], n, "doppler");
+    const float* power = single_real(prhs[5], n, "power");
+    const mwSize sw = (mwSize)fmcw_track_state_bytes(q.max_trk) / 4;   /* a multiple of 16 bytes: int32 words */
+    /* the state comes back as output 11: a copy of the input state carried on, or a fresh (zero) one;
+       MATLAB frees the array itself when it is not returned */
+    mxArray* st = NULL;
+    const int carried = nrhs == 10 && mxGetNumberOfElements(prhs[9]) > 0;
+    if (carried && (!mxIsInt32(prhs[9]) || mxGetNumberOfElements(prhs[9]) != sw * (mwSize)S))
+      mexErrMsgIdAndTxt("fmcw:arg", "state must be int32, fmcw_track_state_bytes(max_trk)/4 x nseq");
+    if (carried || nlhs > 10) st = mxCreateNumericMatrix(sw, (mwSize)S, mxINT32_CLASS, mxREAL);
+    if (carried) memcpy(mxGetInt32s(st), mxGetInt32s(prhs[9]), sw * (size_t)S * 4);
+    /* outputs past nlhs do not exist: their pointers stay NULL and the library leaves them out */
+    const int want = nlhs > 1 ? nlhs : 1;
+    void* o[10] = {0};
+    for (int i = 0; i < 10 && i < want; ++i) {
+      const int is_f = i >= 5 && i <= 8;
+      plhs[i] = mxCreateNumericMatrix(i == 0 ? 1 : i == 9 ? M : T, (mwSize)rows, is_f ? mxSINGLE_CLASS : mxINT32_CLASS, mxREAL);
+      o[i] = is_f ? (void*)mxGetSingles(plhs[i]) : (void*)mxGetInt32s(plhs[i]);
+    }
+    fmcw_tracks t;
+    t.trk_count = (int32_t*)o[0];
+    t.trk_id = (int32_t*)o[1];
+    t.trk_status = (int32_t*)o[2];
+    t.trk_age = (int32_t*)o[3];
+    t.trk_misses = (int32_t*)o[4];
+    t.trk_range = (float*)o[5];
+    t.trk_range_rate = (float*)o[6];
+    t.trk_doppler = (float*)o[7];
+    t.trk_power = (float*)o[8];
+    check(fmcw_track(g_ctx, &q, S, F, nr, nd, (int32_t)M, mxGetInt32s(prhs[2]), range, doppler, power,
+                     st ? (void*)mxGetInt32s(st) : NULL, &t, (int32_t*)o[9]));
+    if (nlhs > 10) plhs[10] = st;
     return;
   }
   mexErrMsgIdAndTxt("fmcw:arg", "unknown command '%s'", cmd);
