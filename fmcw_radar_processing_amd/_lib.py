@@ -20,9 +20,10 @@ FMCW_PIPE_AUTO, FMCW_PIPE_STREAMS, FMCW_PIPE_ONEPASS, FMCW_PIPE_XCD = 0, 1, 3, 4
 ABI_VERSION = 4
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_HIP", -3: "E_OOM", -4: "E_STATE", -5: "E_DATA"}
 STAGES = ("range", "doppler", "detect", "compact", "stft_power", "stft_db", "range_only", "range_doppler", "onepass",
-          "render", "cfar", "cluster", "track")
+          "render", "cfar", "cluster", "track", "mti")
 FMCW_CFAR_LOCAL_MAX = 1
 FMCW_SIG_DB = 1
+FMCW_MTI_RAMP, FMCW_MTI_FREEZE = 1, 2
 
 
 class FmcwError(RuntimeError):
@@ -89,6 +90,11 @@ class Tracks(ct.Structure):
 
 TRACK_INT_KEYS = ("trk_id", "trk_status", "trk_age", "trk_misses")
 TRACK_FLOAT_KEYS = ("trk_range", "trk_range_rate", "trk_doppler", "trk_power")
+
+
+class MtiParams(ct.Structure):
+    """fmcw_mti_params (include/fmcw.h)."""
+    _fields_ = [("lambda_", ct.c_float), ("flags", ct.c_int32)]
 
 
 class JsonField(ct.Structure):
@@ -158,6 +164,10 @@ SIGNATURES = {
                                      ct.POINTER(Tracks), _P, _P]),
     "fmcw_track": (ct.c_int, [_P, ct.POINTER(TrackParams), _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P,
                               ct.POINTER(Tracks), _P]),
+    "fmcw_mti_check": (ct.c_int, [ct.POINTER(MtiParams), _I32, _I32]),
+    "fmcw_mti_ring": (_I32, [_I32]),
+    "fmcw_mti_device": (ct.c_int, [_P, ct.POINTER(MtiParams), _P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P, _P]),
+    "fmcw_mti": (ct.c_int, [_P, ct.POINTER(MtiParams), _P, _I32, _I64, _I64, _I32, _I32, _P, _P, _P]),
     "fmcw_json_write": (ct.c_int, [ct.c_char_p, ct.POINTER(JsonField), _I32, _I32, _I32, ct.POINTER(_I64)]),
     "fmcw_stft_png": (ct.c_int, [_P, _P, _I64, _P, _I32, _I32, _I32, _D, _I32, _P, _P, _P, ct.c_char_p, _I32, _I32,
                                  ct.POINTER(_I64)]),

@@ -177,7 +177,7 @@ void shard(int64_t total, int g, int world, int64_t& f0, int64_t& n) {
   n = base + (g < rem ? 1 : 0);
 }
 
-constexpr int kStages = 13;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar, 11 cluster, 12 track
+constexpr int kStages = 14;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar, 11 cluster, 12 track, 13 mti
 
 }  // namespace
 
@@ -332,6 +332,8 @@ struct fmcw_ctx {
   DevBuf cl_in, cl_out;
   // fmcw_track (host pointers): the chunk's target rows, the chunk's outputs and the sequences' state on the device
   DevBuf tk_in, tk_out, tk_state;
+  // fmcw_mti (host pointers): the chunk's frames (filtered in place) and the sequences' state on the device
+  DevBuf mt_rd, mt_bg, mt_seen;
   int64_t chunk_frames = 0;
   int64_t last_coarse_tiles = -1;     // tiles the last coarse-to-fine max(P) evaluated in full (diagnostics)
   int pipe_mode = FMCW_PIPE_AUTO;
@@ -2703,6 +2705,142 @@ int fmcw_track(fmcw_ctx* c, const fmcw_track_params* q, int64_t S, int64_t F, in
     return track_host_one(d, q, n, F, nr, nd, max_tgt, count + r0, range + r0 * M, doppler + r0 * M, power + r0 * M,
                           state ? static_cast<char*>(state) + (size_t)s0 * sbytes : nullptr, t,
                           tgt_track ? tgt_track + r0 * M : nullptr);
+  });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Frame-to-frame clutter filter of the RD map (kernels_mti.hip)
+// ---------------------------------------------------------------------------
+static int mti_check_impl(const fmcw_mti_params* q, int32_t nr, int32_t nd) {
+  if (!q) return fail(FMCW_E_ARG, "mti params is NULL");
+  if (nr < 16 || nr > 2048 || (nr & (nr - 1))) return fail(FMCW_E_ARG, "mti: nr must be a power of two in [16, 2048]");
+  if (nd < 4 || nd > 1024 || (nd & (nd - 1))) return fail(FMCW_E_ARG, "mti: nd must be a power of two in [4, 1024]");
+  if (!(std::isfinite(q->lambda) && q->lambda > 0.f && q->lambda <= 1.f))
+    return fail(FMCW_E_ARG, "mti: lambda must be finite and in (0, 1]");
+  if (q->flags & ~(FMCW_MTI_RAMP | FMCW_MTI_FREEZE)) return fail(FMCW_E_ARG, "mti: unknown flag bits");
+  return FMCW_OK;
+}
+
+// frames per lane in flight: the shipped depth of the dtype (FMCW_MTI_RING, one of 4 8 16,
+// overrides, for the measurement of tools/bench_mti.py)
+static int mti_ring(int32_t dtype) {
+  if (const char* e = std::getenv("FMCW_MTI_RING"); e && fmcw::mti_ring_ok(std::atoi(e))) return std::atoi(e);
+  return dtype == FMCW_C32H ? fmcw::kMtiRingC32H : fmcw::kMtiRingC64;
+}
+
+static int mti_sizes(int64_t S, int64_t F) {
+  if (F < 0 || S < 0) return fail(FMCW_E_ARG, "S < 0 or F < 0");
+  if (S > 0x7fffffffLL || F > ((int64_t)1 << 40) / std::max<int64_t>(S, 1))
+    return fail(FMCW_E_ARG, "mti: S must be below 2^31 and S * F at most 2^40");
+  return FMCW_OK;
+}
+
+// frames [f0, f0 + nf) of every one of S sequences, between a host array of F frames per sequence
+// and a dense device array of nf frames per sequence
+static int mti_frames(char* dev, char* host, int64_t S, int64_t F, int64_t f0, int64_t nf, size_t fbytes, bool to_device,
+                      hipStream_t s) {
+  const int64_t runs = nf == F ? 1 : S, per = nf == F ? S * nf : nf;
+  for (int64_t q = 0; q < runs; ++q) {
+    char* const h = host + ((size_t)q * F + f0) * fbytes;
+    char* const d = dev + (size_t)q * nf * fbytes;
+    if (to_device) HIPCHK(hipMemcpyAsync(d, h, (size_t)per * fbytes, hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemcpyAsync(h, d, (size_t)per * fbytes, hipMemcpyDeviceToHost, s));
+  }
+  return FMCW_OK;
+}
+
+static int mti_host_one(fmcw_ctx* c, const fmcw_mti_params* q, const char* rd, int32_t dtype, int64_t S, int64_t F, int32_t nr,
+                        int32_t nd, float* bg, int32_t* seen, char* out) {
+  CHK(set_device(c));
+  hipStream_t s = c->stream;
+  const size_t fin = (size_t)nr * nd * esize(dtype), bbytes = (size_t)nr * nd * 8;
+  // frames per chunk: a chunk holds that many frames of every sequence of the shard
+  const int64_t Fc = host_chunk((size_t)S * fin, F);
+  CHK(c->mt_rd.ensure((size_t)S * Fc * fin));
+  CHK(c->mt_bg.ensure((size_t)S * bbytes));
+  CHK(c->mt_seen.ensure((size_t)S * 4));
+  if (bg) {
+    HIPCHK(hipMemcpyAsync(c->mt_bg.p, bg, (size_t)S * bbytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->mt_seen.p, seen, (size_t)S * 4, hipMemcpyHostToDevice, s));
+  } else {
+    HIPCHK(hipMemsetAsync(c->mt_bg.p, 0, (size_t)S * bbytes, s));
+    HIPCHK(hipMemsetAsync(c->mt_seen.p, 0, (size_t)S * 4, s));
+  }
+  char* const d = c->mt_rd.as<char>();
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    const int64_t nf = std::min(Fc, F - f0);
+    CHK(mti_frames(d, const_cast<char*>(rd), S, F, f0, nf, fin, true, s));
+    CHK(fmcw_mti_device(c, q, d, dtype, S, nf, nr, nd, c->mt_bg.as<float>(), c->mt_seen.as<int32_t>(), out ? d : nullptr, s));
+    if (out) CHK(mti_frames(d, out, S, F, f0, nf, fin, false, s));
+    HIPCHK(hipStreamSynchronize(s));           // the chunk buffer is reused by the next chunk
+  }
+  if (bg) {
+    HIPCHK(hipMemcpyAsync(bg, c->mt_bg.p, (size_t)S * bbytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(seen, c->mt_seen.p, (size_t)S * 4, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  return FMCW_OK;
+}
+
+extern "C" {
+
+int fmcw_mti_check(const fmcw_mti_params* q, int32_t nr, int32_t nd) { return mti_check_impl(q, nr, nd); }
+
+int32_t fmcw_mti_ring(int32_t rd_dtype) {
+  if (rd_dtype != FMCW_C64 && rd_dtype != FMCW_C32H) return fail(FMCW_E_ARG, "bad rd_dtype");
+  return mti_ring(rd_dtype);
+}
+
+int fmcw_mti_device(fmcw_ctx* c, const fmcw_mti_params* q, const void* d_rd, int32_t rd_dtype, int64_t S, int64_t F,
+                    int32_t nr, int32_t nd, float* d_bg, int32_t* d_seen, void* d_out, void* stream) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(mti_check_impl(q, nr, nd));
+  if (rd_dtype != FMCW_C64 && rd_dtype != FMCW_C32H) return fail(FMCW_E_ARG, "bad rd_dtype");
+  CHK(mti_sizes(S, F));
+  if ((q->flags & FMCW_MTI_FREEZE) && !d_out) return fail(FMCW_E_ARG, "mti: FREEZE without an output leaves nothing to do");
+  if (F == 0 || S == 0) return FMCW_OK;
+  if (!d_rd || !d_bg || !d_seen) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const uintptr_t pr = reinterpret_cast<uintptr_t>(d_rd), po = reinterpret_cast<uintptr_t>(d_out);
+  if ((pr | po | reinterpret_cast<uintptr_t>(d_bg) | reinterpret_cast<uintptr_t>(d_seen)) & 15)
+    return fail(FMCW_E_ARG, "mti: d_rd, d_out, d_bg and d_seen must be 16-byte aligned");
+  const size_t fin = (size_t)nr * nd * esize(rd_dtype), total = (size_t)S * F * fin;
+  if (d_out && po != pr && po < pr + total && pr < po + total)
+    return fail(FMCW_E_ARG, "mti: d_out must be d_rd itself or not overlap it");
+  CHK(set_device(c));
+  hipStream_t s = pick(c, stream);
+  fmcw::MtiArgs a{};
+  a.rd = d_rd; a.out = d_out; a.bg = d_bg; a.seen = d_seen;
+  a.S = S; a.F = F;
+  a.n16 = (int64_t)(fin / 16);
+  a.h = rd_dtype == FMCW_C32H;
+  a.ring = mti_ring(rd_dtype);
+  a.lambda = q->lambda;
+  a.ramp = (q->flags & FMCW_MTI_RAMP) ? 1 : 0;
+  a.freeze = (q->flags & FMCW_MTI_FREEZE) ? 1 : 0;
+  StageTimer tm(c, 13, s);
+  HIPCHK(fmcw::launch_mti(a, s));
+  tm.done();
+  return FMCW_OK;
+}
+
+int fmcw_mti(fmcw_ctx* c, const fmcw_mti_params* q, const void* rd, int32_t rd_dtype, int64_t S, int64_t F, int32_t nr,
+             int32_t nd, float* bg, int32_t* seen, void* out) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(mti_check_impl(q, nr, nd));
+  if (rd_dtype != FMCW_C64 && rd_dtype != FMCW_C32H) return fail(FMCW_E_ARG, "bad rd_dtype");
+  CHK(mti_sizes(S, F));
+  if ((q->flags & FMCW_MTI_FREEZE) && !out) return fail(FMCW_E_ARG, "mti: FREEZE without an output leaves nothing to do");
+  if ((bg == nullptr) != (seen == nullptr)) return fail(FMCW_E_ARG, "mti: bg and seen must both be given or both be NULL");
+  if (F == 0 || S == 0) return FMCW_OK;
+  if (!rd) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const size_t fin = (size_t)nr * nd * esize(rd_dtype), cells2 = (size_t)nr * nd * 2;
+  // the frames of a sequence depend on each other, the sequences do not: contiguous shards of sequences
+  return over_devices(c, S, [&](fmcw_ctx* d, int, int64_t s0, int64_t n) {
+    return mti_host_one(d, q, static_cast<const char*>(rd) + (size_t)s0 * F * fin, rd_dtype, n, F, nr, nd,
+                        bg ? bg + (size_t)s0 * cells2 : nullptr, seen ? seen + s0 : nullptr,
+                        out ? static_cast<char*>(out) + (size_t)s0 * F * fin : nullptr);
   });
 }
 

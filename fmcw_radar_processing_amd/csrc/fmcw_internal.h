@@ -389,6 +389,25 @@ struct TrackArgs {
 };
 hipError_t launch_track(const TrackArgs& a, hipStream_t s);
 
+// Frame-to-frame clutter filter of the RD map (kernels_mti.hip): k_mti + k_mti_seen
+constexpr int kMtiRingC64 = 4;     // frames a lane keeps in flight ahead of the recursion
+constexpr int kMtiRingC32H = 8;
+struct MtiArgs {
+  const void* rd;          // [S*F][NR][ND] c64 or c32h; 16-byte aligned
+  void* out;               // the same shape and dtype, == rd (in place), or nullptr: learn only
+  float* bg;               // [S][NR][ND] complex float32, read and (unless freeze) rewritten
+  int32_t* seen;           // [S], advanced by k_mti_seen (unless freeze)
+  int64_t S, F;
+  int64_t n16;             // 16-byte pieces of one frame
+  int bpf;                 // 256-thread blocks of one frame (set by launch_mti)
+  int h;                   // fp16 storage
+  int ring;                // 4, 8 or 16
+  float lambda;
+  int ramp, freeze;
+};
+bool mti_ring_ok(int ring);
+hipError_t launch_mti(const MtiArgs& a, hipStream_t s);
+
 bool range_size_supported(int nr);
 bool doppler_size_supported(int nd);
 

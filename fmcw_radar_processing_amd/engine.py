@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import FMCW_C32H, FMCW_C64, STAGES, FmcwError, check
-from .params import CfarConfig, ClusterConfig, FmcwConfig, SigConfig, TrackConfig
+from .params import CfarConfig, ClusterConfig, FmcwConfig, MtiConfig, SigConfig, TrackConfig
 
 
 def _ptr(a) -> ct.c_void_p:
@@ -524,6 +524,72 @@ class Engine:
                                     probe_column=probe_column, stream=stream)
         self.track_device(q_track, 1, F, cfg.nr, cfg.nd, q_cluster.max_tgt, tgt_outs, d_state, trk_outs,
                           d_tgt_track=d_tgt_track, stream=stream)
+
+    # ---- frame-to-frame clutter filter of the RD map (include/fmcw.h, fmcw_mti_params) ---------
+    def mti_ring(self, rd_dtype: int = FMCW_C64) -> int:
+        """fmcw_mti_ring: the frames a lane of k_mti keeps in flight for that dtype."""
+        n = self.lib.fmcw_mti_ring(int(rd_dtype))
+        if n < 0:
+            check(n)
+        return n
+
+    def mti(self, rd: np.ndarray, q: MtiConfig, n_seq: int = 1, bg: np.ndarray | None = None,
+            seen: np.ndarray | None = None, want_out: bool = True) -> dict:
+        """The filtered map of rd: complex64 [S*F][nr][nd], or float16 [S*F][nr][nd][2] holding
+        D / (nr nd) -- n_seq = S independent sequences of F consecutive frames each, sequence s in the
+        frames s*F .. s*F + F - 1.  Host arrays; the sequences are sharded over the context's devices.
+        bg (complex64 [S][nr][nd]) and seen (int32 [S]): None for fresh sequences, or what an earlier
+        call returned, to carry the sequences on (both or neither; the caller's arrays are not written
+        through).  Returns `out` (the shape and dtype of rd; None without want_out, which only learns
+        the background), `bg` and `seen` after the last frame."""
+        if rd.dtype == np.complex64 and rd.ndim == 3:
+            rd, dt = np.ascontiguousarray(rd), FMCW_C64
+        elif rd.dtype == np.float16 and rd.ndim == 4 and rd.shape[-1] == 2:
+            rd, dt = np.ascontiguousarray(rd), FMCW_C32H
+        else:
+            raise TypeError("rd must be complex64 [S*F][nr][nd] or float16 [S*F][nr][nd][2]")
+        rows, nr, nd = rd.shape[:3]
+        S = int(n_seq)
+        if S < 1 or rows % S:
+            raise ValueError("n_seq must divide the number of frames")
+        if (bg is None) != (seen is None):
+            raise ValueError("bg and seen must both be given or both be None")
+        if bg is None:
+            b, n = np.zeros((S, nr, nd), np.complex64), np.zeros(S, np.int32)
+        else:
+            b = np.array(bg, dtype=np.complex64, order="C", copy=True)
+            n = np.array(seen, dtype=np.int32, order="C", copy=True).reshape(-1)
+            if b.shape != (S, nr, nd) or n.shape != (S,):
+                raise ValueError(f"bg must be complex64 [{S}][{nr}][{nd}] and seen int32 [{S}]")
+        out = np.empty_like(rd) if want_out else None
+        qa = q.abi()
+        check(self.lib.fmcw_mti(self.h, ct.byref(qa), _ptr(rd), dt, S, rows // S, nr, nd, _ptr(b), _ptr(n), _ptr(out)))
+        return dict(out=out, bg=b, seen=n)
+
+    def mti_device(self, q: MtiConfig, d_rd, rd_dtype: int, S: int, F: int, nr: int, nd: int, d_bg, d_seen, d_out=None,
+                   stream=None) -> None:
+        """fmcw_mti_device: d_rd [S*F][nr][nd] of rd_dtype on the device; d_bg [S][nr][nd] complex64
+        and d_seen [S] int32, read and rewritten in place (zeros: fresh sequences); d_out of the shape
+        and dtype of d_rd, d_rd itself (in place), or None: only the background is learned.  q: an
+        MtiConfig, or the C struct _lib.MtiParams itself.  Asynchronous on `stream`."""
+        qa = q.abi() if hasattr(q, "abi") else q
+        with _sided(stream) as hs:
+            check(self.lib.fmcw_mti_device(self.h, ct.byref(qa), _ptr(d_rd), int(rd_dtype), int(S), int(F), int(nr),
+                                           int(nd), _ptr(d_bg), _ptr(d_seen), _ptr(d_out), hs))
+
+    def process_mti_device(self, d_iq, F: int, in_dtype: int, outs: dict, q: MtiConfig, d_rd, d_bg, d_seen, d_out=None,
+                           out_dtype: int = FMCW_C64, d_cube=None, probe_column: int = 0, stream=None) -> None:
+        """IQ in, filtered RD map out, on one stream with no host round trip: process_device writing
+        the RD map to d_rd (out_dtype), then mti_device over the F frames as one sequence, carried on
+        from d_bg / d_seen.  d_out None: in place in d_rd.  cfar_device, signature_device and
+        cluster_device / track_device then chain on the filtered buffer as they are."""
+        cfg = self._need()
+        if d_rd is None:
+            raise ValueError("process_mti_device needs an RD buffer")
+        self.process_device(d_iq, F, in_dtype, outs, d_cube=d_cube, d_rd=d_rd, out_dtype=out_dtype,
+                            probe_column=probe_column, stream=stream)
+        self.mti_device(q, d_rd, out_dtype, 1, F, cfg.nr, cfg.nd, d_bg, d_seen, d_out=d_rd if d_out is None else d_out,
+                        stream=stream)
 
     # ---- timing -----------------------------------------------------------------
     def timing(self, level: int) -> None:

@@ -12,7 +12,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import windows
-from ._lib import FMCW_CFAR_LOCAL_MAX, FMCW_SIG_DB, CfarParams, ClusterParams, Params, SigParams, TrackParams
+from ._lib import (FMCW_CFAR_LOCAL_MAX, FMCW_MTI_FREEZE, FMCW_MTI_RAMP, FMCW_SIG_DB, CfarParams, ClusterParams, MtiParams,
+                   Params, SigParams, TrackParams)
 
 C0 = 3e8  # radar_processing.m:67
 
@@ -398,3 +399,29 @@ def config(name, **over) -> FmcwConfig:
     cfg = derive_params(deployed_device(c["nts"], c["pn"]), nr=c["nr"], nd=c["nd"], mode=c["mode"])
     cfg.extra = {k: v for k, v in c.items() if k not in ("nts", "pn", "nr", "nd", "mode")}
     return cfg
+
+
+@dataclass
+class MtiConfig:
+    """fmcw_mti_params (include/fmcw.h): the frame-to-frame clutter filter of the RD map.  A complex
+    background per cell follows the frames with gain lambda_ (1: the two-frame canceller) and is
+    subtracted coherently.  ramp: the gain starts at 1 / (frames seen + 1), the running mean, and
+    settles at lambda_.  freeze: subtract the learned background without updating it."""
+    lambda_: float = 0.05
+    ramp: bool = True
+    freeze: bool = False
+
+    def abi(self) -> MtiParams:
+        return MtiParams(self.lambda_, (FMCW_MTI_RAMP if self.ramp else 0) | (FMCW_MTI_FREEZE if self.freeze else 0))
+
+    def validate(self, nr: int, nd: int) -> None:
+        """The rules of fmcw_mti_check, on the float32 value the C struct carries; ValueError naming
+        the first one violated."""
+        if nr < 16 or nr > 2048 or nr & (nr - 1):
+            raise ValueError("mti: nr must be a power of two in [16, 2048]")
+        if nd < 4 or nd > 1024 or nd & (nd - 1):
+            raise ValueError("mti: nd must be a power of two in [4, 1024]")
+        with np.errstate(over="ignore"):
+            lam = np.float32(self.lambda_)
+        if not (np.isfinite(lam) and 0 < lam <= 1):
+            raise ValueError("mti: lambda must be finite and in (0, 1]")

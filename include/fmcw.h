@@ -49,7 +49,9 @@ extern "C" {
  *    same way
  *    + the tracking entry points (fmcw_track_check, fmcw_track_state_bytes, fmcw_track_device,
  *    fmcw_track), the structs fmcw_track_params / fmcw_tracks and timing stage 12, added within
- *    ABI 4 in the same way */
+ *    ABI 4 in the same way
+ *    + the clutter-filter entry points (fmcw_mti_check, fmcw_mti_ring, fmcw_mti_device, fmcw_mti),
+ *    the struct fmcw_mti_params and timing stage 13, added within ABI 4 in the same way */
 #define FMCW_ABI_VERSION 4
 
 typedef enum fmcw_status {
@@ -276,7 +278,8 @@ int fmcw_synth_device(fmcw_ctx* ctx, const fmcw_params* p, int64_t frame0, int64
  *        6 range_only, 7 range+Doppler span, 8 k_rdx (single-pass schedule,
  *        level 2), 9 render (spectrogram.png), 10 cfar (one pair per k_cfar + k_cfar_gather
  *        launch pair of fmcw_cfar_device), 11 cluster (one pair per k_cluster launch of
- *        fmcw_cluster_device), 12 track (one pair per k_track launch of fmcw_track_device).
+ *        fmcw_cluster_device), 12 track (one pair per k_track launch of fmcw_track_device),
+ *        13 mti (one pair per fmcw_mti_device call's k_mti + k_mti_seen launches).
  *        fmcw_timing_read synchronises. */
 int fmcw_timing_enable(fmcw_ctx* ctx, int32_t enable);
 int fmcw_timing_read(fmcw_ctx* ctx, int32_t stage, double* total_ms, int64_t* launches);
@@ -637,6 +640,86 @@ int fmcw_track_device(fmcw_ctx* ctx, const fmcw_track_params* q, int64_t S, int6
 int fmcw_track(fmcw_ctx* ctx, const fmcw_track_params* q, int64_t S, int64_t F, int32_t nr, int32_t nd,
                int32_t max_tgt, const int32_t* tgt_count, const float* range, const float* doppler,
                const float* peak_power, void* state, const fmcw_tracks* out, int32_t* tgt_track);
+
+/* ---------------------------------------------------------------------------
+ * Frame-to-frame clutter filter (MTI) of the range-Doppler map (added within ABI 4; beyond the
+ * reference, which has no moving-target step: the Doppler mean removal of :217-218 cancels only
+ * what is constant within one frame).  A complex background per RD cell is learned recursively and
+ * subtracted coherently: whatever repeats from frame to frame -- walls, rails, feeders and their
+ * leakage into every Doppler bin -- goes, whatever changes its phase from frame to frame stays.
+ * The output is an RD map in the layout and dtype of the input, so fmcw_cfar*, fmcw_sig* and
+ * everything behind them take it unchanged.
+ *   Input: rd [S*F][nr][nd] in the layout fmcw_process* writes, FMCW_C64 or FMCW_C32H: S
+ *     independent sequences of F consecutive frames each; frame f of sequence s is frame s*F + f, as
+ *     in fmcw_track.  nr, nd within CFAR's limits.
+ *   State per sequence, public layout, always float32:
+ *     bg   [S][nr][nd] complex64 interleaved: the background B, in the units of the stored values
+ *          (fp16 storage: D/(nr*nd)).
+ *     seen [S] int32: the number of frames absorbed.
+ *     An all-zero bg with seen = 0 is a fresh sequence.  A caller may save the state, reload it and
+ *     inspect it (which is why the layout is public, unlike the tracker's).
+ *   Parameters: lambda finite, in (0, 1]; no unknown flag bit; FMCW_MTI_FREEZE together with a NULL
+ *     output is FMCW_E_ARG (there would be nothing to do); RAMP with FREEZE is allowed, RAMP is then
+ *     moot.
+ *   One frame step for every cell, re and im handled separately, in float32, every operation rounded
+ *   on its own in the order written (no fused multiply-add):
+ *   1. x is the stored value; fp16 storage is widened exactly to float32.
+ *   2. y = x - B.  The output cell of this frame is y; for FMCW_C32H it is converted with IEEE
+ *      round-to-nearest-even, subnormals kept (exactly numpy's astype(float16)).
+ *   3. Update, unless FMCW_MTI_FREEZE is set: n = clamp(seen, 0, 2^30); with FMCW_MTI_RAMP
+ *      g = max(lambda, 1.0f / (float)(n + 1)), without it g = lambda; if g == 1.0f then B = x,
+ *      otherwise t = g*y, then B = B + t.
+ *   4. After the frame seen = min(n + 1, 2^30).  With FREEZE, B and seen are not touched.
+ *   So lambda = 1 is the exact two-frame canceller D_f - D_{f-1}; RAMP starts as the running mean of
+ *   the frames so far and goes over to the exponential average after about 1/lambda frames (from a
+ *   fresh state frame 0 passes unchanged and B becomes frame 0 exactly); FREEZE subtracts a learned
+ *   background without touching it ("learn the empty pen, then watch").
+ *   Results are bit-identical from call to call.  A sequence's results do not depend on S or on which
+ *   other sequences share the call.  F frames in one call equal any split into consecutive calls with
+ *   bg / seen carried, byte for byte, in the output and in the final state.  For finite input every
+ *   output and state bit equals the numpy float32 evaluation of the steps above (g has the bits of
+ *   float32(1)/float32(n+1): a correctly rounded division).  A non-finite input value makes that
+ *   cell's output and background unspecified from then on (NaN payloads differ between hosts and the
+ *   GPU); it touches no other cell and nothing out of bounds.
+ *   Measured on one MI355X over 4096 frames of 1024 x 256, S = 1 (profiles/mti_bench.json, 2026-10-20,
+ *   tree ad9069a+), beside fmcw_copy_device over the same RD bytes in the same run (2.64 ms FMCW_C64,
+ *   1.31 ms FMCW_C32H), which reads and writes what the filter with an output reads and writes: to a
+ *   second buffer 3.43 / 1.56 ms (1.30x / 1.19x the copy), in place 3.17 / 1.57 ms (1.20x / 1.20x), 64
+ *   sequences of 64 frames 3.28 / 1.50 ms (1.24x / 1.14x): with an output the stage MISSES the
+ *   copy-time yardstick by 14-30 %.  Learning only (no output, half the bytes) takes 1.40 / 0.65 ms,
+ *   0.53x / 0.50x the copy against a goal of 0.5: it meets it in fp16 storage and misses it by 6 % in
+ *   complex64 (what was tried, and what the evidence excludes as the bound).
+ * ------------------------------------------------------------------------- */
+enum { FMCW_MTI_RAMP = 1, FMCW_MTI_FREEZE = 2 };
+typedef struct fmcw_mti_params {
+  float   lambda;          /* (0, 1], finite */
+  int32_t flags;           /* FMCW_MTI_RAMP | FMCW_MTI_FREEZE */
+} fmcw_mti_params;
+
+/* Host only, no context.  fmcw_mti_check: FMCW_E_ARG (with a message) for a lambda or flags outside
+ * the rules above or nr / nd outside CFAR's limits.  fmcw_mti_ring: the number of frames U a lane of
+ * k_mti keeps in flight ahead of the recursion for that dtype (the frame counts at which the kernel
+ * changes path are U and 2U), or FMCW_E_ARG for an unknown dtype. */
+int fmcw_mti_check(const fmcw_mti_params* q, int32_t nr, int32_t nd);
+int32_t fmcw_mti_ring(int32_t rd_dtype);
+
+/* Device pointers, each 16-byte aligned; asynchronous on `stream`; needs no fmcw_set_taps.  Acts on
+ * the context's first device.  d_bg [S][nr][nd] complex64 and d_seen [S] are read and rewritten in
+ * place.  d_out has the dtype of d_rd; d_out == d_rd (in place) is allowed (a lane writes only the
+ * addresses it has already read), a partial overlap is FMCW_E_ARG; d_out == NULL learns the
+ * background and writes no map.  F = 0 or S = 0 is a no-op.  FMCW_E_ARG is returned before any
+ * launch: the outputs and the state are then untouched. */
+int fmcw_mti_device(fmcw_ctx* ctx, const fmcw_mti_params* q, const void* d_rd, int32_t rd_dtype,
+                    int64_t S, int64_t F, int32_t nr, int32_t nd, float* d_bg, int32_t* d_seen,
+                    void* d_out, void* stream);
+
+/* Host pointers.  bg and seen are both given (read and rewritten) or both NULL: the sequences start
+ * fresh and the state is discarded.  out may be NULL (learn only).  Sequences, never frames, are
+ * sharded contiguously over the context's devices (S = 1 runs on the first device); the frames are
+ * staged in chunks with bg / seen kept on the device between chunks (bit-identical, by the split
+ * guarantee above).  Returns when the outputs are on the host. */
+int fmcw_mti(fmcw_ctx* ctx, const fmcw_mti_params* q, const void* rd, int32_t rd_dtype,
+             int64_t S, int64_t F, int32_t nr, int32_t nd, float* bg, int32_t* seen, void* out);
 
 /* ---------------------------------------------------------------------------
  * spectrogram.png, replacing radar_processing.m:331-348:

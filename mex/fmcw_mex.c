@@ -52,6 +52,16 @@
  *                                        an earlier call returned it, or absent / [] for fresh sequences; kcnt is
  *                                        1 x (nseq*F), tgt_track max_tgt x (nseq*F), the others max_trk x (nseq*F):
  *                                        a row is the trajectory of one slot.  Outputs not asked for are not computed.
+ *   [out, bg, seen] = fmcw_mex('mti', Q, rd, nseq[, bg, seen])    -> fmcw_mti: the frame-to-frame clutter filter
+ *                                        of an RD map (beyond the reference): a complex background per cell,
+ *                                        learned recursively and subtracted coherently; Q: a struct with the fields
+ *                                        of fmcw_mti_params (lambda, flags); rd as for 'cfar', Nd x Nr x (nseq*F)
+ *                                        (sequence s in the frames s*F+1 .. s*F+F); bg: single complex Nd x Nr x
+ *                                        nseq and seen: int32 1 x nseq as an earlier call returned them, or both
+ *                                        absent / [] for fresh sequences; out is (Nd*Nr) x (nseq*F) and bg (Nd*Nr) x
+ *                                        nseq, single complex (reshape(out, Nd, Nr, []) feeds 'cfar' and 'signature'
+ *                                        unchanged), seen 1 x nseq.  With FMCW_MTI_FREEZE in Q.flags bg and seen
+ *                                        come back as they went in.
  *   fmcw_mex('close')                                             -> fmcw_ctx_destroy
  *
  * P is a struct with the fields of fmcw_params (nts, pn, nr, nd, max_targets,
@@ -419,6 +429,41 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     check(fmcw_track(g_ctx, &q, S, F, nr, nd, (int32_t)M, mxGetInt32s(prhs[2]), range, doppler, power,
                      st ? (void*)mxGetInt32s(st) : NULL, &t, (int32_t*)o[9]));
     if (nlhs > 10) plhs[10] = st;
+    return;
+  }
+  if (!strcmp(cmd, "mti")) {                /* [out, bg, seen] = fmcw_mex('mti', Q, rd, nseq[, bg, seen]) */
+    if (nrhs != 4 && nrhs != 6) mexErrMsgIdAndTxt("fmcw:arg", "mti: Q, rd, nseq[, bg, seen]");
+    const mxArray* s = prhs[1];
+    const mxArray* rd = prhs[2];
+    if (!mxIsStruct(s)) mexErrMsgIdAndTxt("fmcw:arg", "Q must be a struct");
+    fmcw_mti_params q;
+    q.lambda = (float)field(s, "lambda");
+    q.flags = (int32_t)field(s, "flags");
+    if (!mxIsSingle(rd) || !mxIsComplex(rd) || mxGetNumberOfDimensions(rd) < 2)
+      mexErrMsgIdAndTxt("fmcw:arg", "rd must be single complex Nd x Nr x (nseq*F)");
+    const mwSize* dims = mxGetDimensions(rd);
+    const int64_t rows = mxGetNumberOfDimensions(rd) >= 3 ? (int64_t)dims[2] : 1;
+    const int32_t nd = (int32_t)dims[0], nr = (int32_t)dims[1];
+    const int64_t S = (int64_t)mxGetScalar(prhs[3]);
+    check(fmcw_mti_check(&q, nr, nd));
+    if (S < 1 || rows % S) mexErrMsgIdAndTxt("fmcw:arg", "nseq must divide the number of frames");
+    const mwSize cells = (mwSize)nd * (mwSize)nr;
+    /* the state comes back as outputs 2 and 3: a copy of the input state carried on, or a fresh (zero) one */
+    const int carried = nrhs == 6 && mxGetNumberOfElements(prhs[4]) > 0;
+    if (carried && (!mxIsSingle(prhs[4]) || !mxIsComplex(prhs[4]) || mxGetNumberOfElements(prhs[4]) != cells * (mwSize)S ||
+                    !mxIsInt32(prhs[5]) || mxGetNumberOfElements(prhs[5]) != (mwSize)S))
+      mexErrMsgIdAndTxt("fmcw:arg", "bg must be single complex Nd x Nr x nseq and seen int32 with nseq entries");
+    plhs[0] = mxCreateNumericMatrix(cells, (mwSize)rows, mxSINGLE_CLASS, mxCOMPLEX);
+    mxArray* bg = mxCreateNumericMatrix(cells, (mwSize)S, mxSINGLE_CLASS, mxCOMPLEX);
+    mxArray* seen = mxCreateNumericMatrix(1, (mwSize)S, mxINT32_CLASS, mxREAL);
+    if (carried) {
+      memcpy(mxGetComplexSingles(bg), mxGetComplexSingles(prhs[4]), cells * (size_t)S * sizeof(mxComplexSingle));
+      memcpy(mxGetInt32s(seen), mxGetInt32s(prhs[5]), (size_t)S * 4);
+    }
+    check(fmcw_mti(g_ctx, &q, mxGetComplexSingles(rd), FMCW_C64, S, rows / S, nr, nd, (float*)mxGetComplexSingles(bg),
+                   mxGetInt32s(seen), mxGetComplexSingles(plhs[0])));
+    if (nlhs > 1) plhs[1] = bg;
+    if (nlhs > 2) plhs[2] = seen;
     return;
   }
   mexErrMsgIdAndTxt("fmcw:arg", "unknown command '%s'", cmd);
