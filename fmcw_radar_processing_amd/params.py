@@ -155,12 +155,10 @@ class CfarConfig:
         cell-averaging value for pfa with the full window's training-cell count."""
         q = cls(guard_r=int(guard[0]), guard_d=int(guard[1]), train_r=int(train[0]), train_d=int(train[1]),
                 max_det=int(max_det), local_max=bool(local_max))
-        i = np.arange(2, cfg.nr)
-        d = (i - 1) * cfg.dist_per_bin
-        sel = i[(d >= cfg.min_d) & (d <= cfg.max_d)]
+        sel = gate_bins(cfg)
         if len(sel) == 0:
             raise ValueError("no range bin lies in [min_d, max_d]")
-        q.r_lo, q.r_hi = int(sel[0]), int(sel[-1])
+        q.r_lo, q.r_hi = int(sel[0]) + 1, int(sel[-1]) + 1
         q.alpha = cls.alpha_for(q.n_train_full, pfa)
         return q
 
@@ -335,6 +333,21 @@ def derive_params(device: dict, nr: int = 256, nd: int = 16, mode: str = PARITY,
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg
+
+
+def gate_bins(cfg: FmcwConfig) -> np.ndarray:
+    """The 0-based range bins the peak rule (:211, f_search_peak) admits, as the kernels compute
+    them (select_peaks in frame_ops.h, k_rdx's candidate keys): bins i in 1..nr-2 with
+    i * dist_per_bin in [min_d, max_d], the product in double from the float32 parameters the
+    C-ABI carries.  When a limit lies on a bin and dist_per_bin is not exact in binary, this
+    gate and the one computed from the Python doubles differ by that bin; the CFAR and
+    signature gates (CfarConfig.for_config) are this one, so all three are one set of rows."""
+    f = np.float32
+    with np.errstate(over="ignore"):
+        dpb, lo, hi = float(f(cfg.dist_per_bin)), float(f(cfg.min_d)), float(f(cfg.max_d))
+    i = np.arange(1, max(cfg.nr - 1, 1))
+    d = i.astype(np.float64) * dpb
+    return i[(d >= lo) & (d <= hi)]
 
 
 def fp16_fp32_bins(cfg: FmcwConfig) -> np.ndarray:
