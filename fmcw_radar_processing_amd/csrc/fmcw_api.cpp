@@ -1,115 +1,35 @@
-// fmcw_api.cpp -- libfmcw C-ABI (include/fmcw.h) on top of the gfx950 kernels.
+// fmcw_api.cpp -- libfmcw C-ABI (include/fmcw.h) on top of the gfx950 kernels: the context
+// and the per-frame pipeline.  The STFT and render path is api_stft.cpp, the RD-map stages
+// (CFAR, signatures, clustering, tracking, MTI) are api_stages.cpp; api_internal.h holds what
+// the three share.
 //
 // Host responsibilities kept here, mirroring what radar_processing.m does
 // around the loop: argument validation (MATLAB would raise), twiddle tables,
-// scratch management for the per-chunk range cube, the chunked launch
-// sequence K1 -> K2 -> K3, the STFT size rules of :273/:276 and the
-// logspace/interp1 bin table of :293-299.
-#include "../../include/fmcw.h"
-#include "fmcw_internal.h"
+// scratch management for the per-chunk range cube and the chunked launch
+// sequence K1 -> K2 -> K3.
+#include "api_internal.h"
 #include "xcd_ctr_plan.h"
 
 #include <dlfcn.h>
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <memory>
-#include <string>
-#include <thread>
-#include <vector>
 
 namespace {
+thread_local std::string g_err;   // the library's one error text (fmcw_last_error)
+}  // namespace
 
-thread_local std::string g_err;
+namespace fmcw {
 
 int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
 
-#define HIPCHK(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) return fail(FMCW_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+int set_error(int code, const char* msg) { return fail(code, msg); }
 
-#define CHK(expr)            \
-  do {                       \
-    int r_ = (expr);         \
-    if (r_ != FMCW_OK) return r_; \
-  } while (0)
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t n = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= n && p) return FMCW_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    if (bytes == 0) bytes = 16;
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(FMCW_E_OOM, "hipMalloc of " + std::to_string(bytes) + " bytes failed");
-    }
-    n = bytes;
-    return FMCW_OK;
-  }
-  template <typename T> T* as() const { return static_cast<T*>(p); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-};
-
-// Offsets of several arrays packed into one buffer (256-byte aligned).
-struct Arena {
-  size_t off = 0;
-  size_t add(size_t bytes) {
-    const size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  }
-};
-
-// Page-locked host staging buffer (DMA source / target of the host-pointer calls).
-struct PinBuf {
-  void* p = nullptr;
-  size_t n = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= n && p) return FMCW_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    n = 0;
-    if (bytes == 0) bytes = 16;
-    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(FMCW_E_OOM, "hipHostMalloc of " + std::to_string(bytes) + " bytes failed");
-    }
-    n = bytes;
-    return FMCW_OK;
-  }
-  char* at(size_t off) const { return static_cast<char*>(p) + off; }
-  PinBuf() = default;
-  PinBuf(const PinBuf&) = delete;
-  PinBuf& operator=(const PinBuf&) = delete;
-  ~PinBuf() {
-    if (p) (void)hipHostFree(p);
-  }
-};
-
-// Host memcpy between the caller's (pageable) arrays and the pinned slots,
-// split over a few threads: one core copies ~10 GB/s, PCIe Gen5 x16 takes ~50.
+// one core copies ~10 GB/s, PCIe Gen5 x16 takes ~50
 void par_memcpy(void* dst, const void* src, size_t n) {
   const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
   const unsigned T = n >= (8u << 20) ? std::min(8u, hw) : 1u;
@@ -126,20 +46,6 @@ void par_memcpy(void* dst, const void* src, size_t n) {
   }
   for (auto& x : th) x.join();
 }
-
-size_t esize(int dtype) { return dtype == FMCW_C32H ? 4 : 8; }
-
-// RCCL, resolved at run time: a single-device context never needs it, and a
-// process that already holds an RCCL (torch's) shares that copy.
-struct Rccl {
-  ncclResult_t (*comm_init_all)(ncclComm_t*, int, const int*) = nullptr;
-  ncclResult_t (*comm_destroy)(ncclComm_t) = nullptr;
-  ncclResult_t (*all_reduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*group_start)() = nullptr;
-  ncclResult_t (*group_end)() = nullptr;
-  const char* (*error_string)(ncclResult_t) = nullptr;
-  bool ok = false;
-};
 
 const Rccl& rccl() {
   static Rccl r = [] {
@@ -164,267 +70,52 @@ const Rccl& rccl() {
   return r;
 }
 
-#define NCCLCHK(expr)                                                                     \
-  do {                                                                                    \
-    ncclResult_t r_ = (expr);                                                             \
-    if (r_ != ncclSuccess) return fail(FMCW_E_HIP, std::string(#expr) + ": " + rccl().error_string(r_)); \
-  } while (0)
-
-// contiguous shard [f0, f0 + n) of `total` items for member g of `world` (dist.py shard_range)
-void shard(int64_t total, int g, int world, int64_t& f0, int64_t& n) {
-  const int64_t base = total / world, rem = total % world;
-  f0 = g * base + std::min<int64_t>(g, rem);
-  n = base + (g < rem ? 1 : 0);
-}
-
-constexpr int kStages = 14;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar, 11 cluster, 12 track, 13 mti
-
-}  // namespace
-
-namespace fmcw {
-int set_error(int code, const char* msg) { return fail(code, msg); }
 }  // namespace fmcw
 
-struct fmcw_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  // software pipeline over chunks: K1 (range) on the caller's stream, K2
-  // (Doppler) on sd, K3 (detect) on sx; chunk i's K2 overlaps chunk i+1's K1
-  static constexpr int kSlots = 3;
-  hipStream_t sd = nullptr, sx = nullptr;
-  hipEvent_t ev_k1[kSlots] = {}, ev_k2[kSlots] = {}, ev_k3[kSlots] = {};
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool taps = false;
-  fmcw_params p{};
-  DevBuf cal, calw, wd, tw_nr, tw_nd;
-  std::vector<float> h_wr, h_cal;   // host copies to rebuild calw when IF_scale changes
-  float calw_scale = 0.f;
-  float2 cal_sum{0.f, 0.f};
-  DevBuf scratch_cube, scratch_rd;
-  // host-pointer API staging: device slots and page-locked host slots, two of
-  // each, so chunk i+1's H2D copy (stream cin) and chunk i-1's D2H copy (cout)
-  // run under chunk i's kernels (the caller's data is copied into the pinned
-  // slots by host threads meanwhile)
-  DevBuf h_iq, h_prof, h_rd;
-  PinBuf pin_in, pin_out;
-  // small per-call arrays of the host-pointer calls, packed so that they cross PCIe as ONE copy
-  // (each pageable copy costs ~20-30 us of latency: six of them were half of a deployed call)
-  DevBuf h_small, s_in;
-  PinBuf pin_small, pin_sin;
-  hipStream_t cin = nullptr, cout = nullptr;
-  hipEvent_t ev_h2d[2] = {}, ev_comp[2] = {}, ev_d2h[2] = {};
-  DevBuf s_P, s_pmax, s_nseg, s_lidx, s_lw, s_out;
-  DevBuf s_cbins, s_segmax, s_tiles;   // fmcw_stft's coarse-to-fine max(P) (stft_coarse_max)
-  DevBuf r_q, r_nseg, r_img;                   // spectrogram.png render (device 0)
-  // Device scratch kept per stream: device calls on different streams (with different windows,
-  // nfft or frame counts) never share one.  At most kPerStream streams per kind (a caller that
-  // passes a fresh stream per call does not grow device memory): the least recently used entry is
-  // taken over, and the new stream first waits for the event recorded behind the old owner's last
-  // readers (done()), so its rewrite cannot overtake them -- the event outlives a destroyed stream.
-  struct PerStream {
-    struct Entry {
-      hipStream_t s = nullptr;
-      DevBuf t;
-      hipEvent_t done = nullptr;
-      uint64_t tick = 0;
-      const void* key = nullptr;   // what the contents were built from (STFT tables: the window pointer)
-      int64_t key_n = 0;           // and its size (the nfft)
-      ~Entry() {
-        if (done) (void)hipEventDestroy(done);
-      }
-    };
-    static constexpr size_t kPerStream = 8;
-    std::vector<std::unique_ptr<Entry>> es;
-    uint64_t tick = 0;
-    void* get(hipStream_t st, size_t bytes, int* status, bool* fresh = nullptr) {
-      Entry* e = nullptr;
-      for (auto& x : es)
-        if (x->s == st) e = x.get();
-      if (!e && es.size() < kPerStream) {
-        es.push_back(std::make_unique<Entry>());
-        e = es.back().get();
-        e->s = st;
-      } else if (!e) {
-        e = es[0].get();
-        for (auto& x : es)
-          if (x->tick < e->tick) e = x.get();
-        if (e->done && hipStreamWaitEvent(st, e->done, 0) != hipSuccess) {
-          (void)hipGetLastError();
-          *status = fail(FMCW_E_HIP, "per-stream scratch: hipStreamWaitEvent failed");
-          return nullptr;
-        }
-        e->s = st;
-        e->key = nullptr;
-        e->key_n = 0;
-      }
-      e->tick = ++tick;
-      void* before = e->t.p;
-      *status = e->t.ensure(bytes);
-      if (e->t.p != before) {                  // newly allocated: its contents are undefined
-        e->key = nullptr;
-        e->key_n = 0;
-      }
-      if (fresh) *fresh = e->t.p != before;
-      last = e;
-      return e->t.p;
-    }
-    Entry* last = nullptr;                     // the entry the last get() returned
-    // after the kernels that read stream st's entry are enqueued
-    int done(hipStream_t st) {
-      for (auto& x : es) {
-        if (x->s != st) continue;
-        if (!x->done && hipEventCreateWithFlags(&x->done, hipEventDisableTiming | fmcw::kEvDevice) != hipSuccess) {
-          (void)hipGetLastError();
-          return fail(FMCW_E_HIP, "per-stream scratch: hipEventCreate failed");
-        }
-        if (hipEventRecord(x->done, st) != hipSuccess) {
-          (void)hipGetLastError();
-          return fail(FMCW_E_HIP, "per-stream scratch: hipEventRecord failed");
-        }
-      }
-      return FMCW_OK;
-    }
-  };
-  // STFT 20-tap tables W[nfft/2+1][20] + the 20 taps they were built from, one per stream that
-  // asked for one
-  PerStream s_tabs;
-  // a table the caller rewrites (any nfft): the entry no longer holds what a cached nfft-64 key
-  // says it holds, so the key is cleared (a later stft_tab64 with the same window rebuilds)
-  float2* stft_tab(hipStream_t st, size_t bytes, int* status) {
-    float2* t = static_cast<float2*>(s_tabs.get(st, bytes + STFT_TAPS_BYTES, status));
-    if (t) {
-      s_tabs.last->key = nullptr;
-      s_tabs.last->key_n = 0;
-    }
-    return t;
-  }
-  static constexpr size_t STFT_TAPS_BYTES = 20 * 4;
-  // The device calls at nfft 64 (the bench's config-4 STFT, two passes per step) keep the
-  // stream's table while the window pointer and nfft are unchanged: k_stft64m compares the 20
-  // taps stored behind the table with the call's window and forms its W entries itself when they
-  // differ (a window rewritten in place), so the table is rebuilt once, not every pass.
-  // *build: the caller must launch k_stft_table into the returned table.
-  float2* stft_tab64(hipStream_t st, const float* d_win, int nfft, bool* build, int* status) {
-    float2* t = static_cast<float2*>(s_tabs.get(st, (size_t)(nfft / 2 + 1) * 20 * 8 + STFT_TAPS_BYTES, status));
-    if (!t) return nullptr;
-    PerStream::Entry* e = s_tabs.last;
-    *build = !(e->key == d_win && e->key_n == nfft);
-    e->key = d_win;
-    e->key_n = nfft;
-    return t;
-  }
-  int stft_tab_done(hipStream_t st) { return s_tabs.done(st); }
-  // K1's per-workgroup profile maxima of fmcw_range_fft_device (config 2), one per stream: two
-  // range-only calls on different streams of one context do not write over each other's partials
-  PerStream k1_part;
-  // k_detect_1p's arrival counter of the fused compaction (fmcw_process_slow_device), one per
-  // stream; zeroed when allocated, reset by the kernel's last workgroup
-  PerStream det_done;
-  // fmcw_cfar_device's per-wave detection lists and counts, one per stream
-  PerStream cfar_scr;
-  // fmcw_cfar (host pointers): the RD chunk, the per-frame outputs and the mask chunk on the device
-  DevBuf cf_in, cf_out, cf_mask;
-  // fmcw_sig_device's per-slab column sums, one per stream
-  PerStream sig_scr;
-  // fmcw_sig (host pointers): the RD chunk, the centres, and both maps with their two maxima on the device
-  DevBuf sg_in, sg_ctr, sg_out;
-  // fmcw_cluster (host pointers): the chunk's detection lists and the per-frame outputs on the device
-  DevBuf cl_in, cl_out;
-  // fmcw_track (host pointers): the chunk's target rows, the chunk's outputs and the sequences' state on the device
-  DevBuf tk_in, tk_out, tk_state;
-  // fmcw_mti (host pointers): the chunk's frames (filtered in place) and the sequences' state on the device
-  DevBuf mt_rd, mt_bg, mt_seen;
-  int64_t chunk_frames = 0;
-  int64_t last_coarse_tiles = -1;     // tiles the last coarse-to-fine max(P) evaluated in full (diagnostics)
-  int pipe_mode = FMCW_PIPE_AUTO;
-  DevBuf op_rowpk, op_cidx, op_crows;           // single-pass schedule scratch (per chunk)
-  DevBuf x_cube, x_ctr, x_err, x_tab;          // XCD-team schedule: hand-off slots, counters, sticky error, XT_* table
-  DevBuf x_clk;                                // k_rdx's clock stamps of its last launch (fmcw_rdx_clock)
-  int xcd_teams = -1;                          // census of the device: its XCD teams (-1 not run yet, 0 none)
-  int8_t xcc_team[16] = {};                    // HW_REG_XCC_ID -> team
-  bool xcd_used = false;                       // a k_rdx launch since the last error check
-  int x_ctr_set = 0;                           // the counter set (0 / 1) of x_ctr the next k_rdx launch counts in
-  bool x_tab_ok = false;                       // x_tab built for the current taps
-  // Multi-device context (fmcw_ctx_create with n_devices > 1): this object is
-  // device 0 of the context and peers[i] a full context on device i + 1.  The
-  // host-pointer calls shard their frames (fmcw_process, fmcw_range_fft) or
-  // spectrogram segments (fmcw_stft) over all of them; the device-pointer
-  // calls act on device 0.  comms: one RCCL communicator per device
-  // (ncclCommInitAll) when the device ids are distinct.
-  std::vector<fmcw_ctx*> peers;
-  std::vector<ncclComm_t> comms;
-  int timing = 0;                    // 0 off, 1 range+Doppler span + STFT launches, 2 + every K1/K2/K3
-  struct Pending {
-    hipEvent_t a, b;
-    int stage;
-  };
-  std::vector<Pending> pending;
-  std::vector<hipEvent_t> pool;
-  double total_ms[kStages] = {};
-  int64_t launches[kStages] = {};
-
-  ~fmcw_ctx() {
-    for (ncclComm_t m : comms) (void)rccl().comm_destroy(m);
-    for (fmcw_ctx* q : peers) delete q;
-    (void)hipSetDevice(device);
-    if (stream) (void)hipStreamSynchronize(stream);
-    for (auto& pd : pending) { (void)hipEventDestroy(pd.a); (void)hipEventDestroy(pd.b); }
-    for (auto e : pool) (void)hipEventDestroy(e);
-    for (int i = 0; i < kSlots; ++i)
-      for (hipEvent_t e : {ev_k1[i], ev_k2[i], ev_k3[i]})
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {ev_fork, ev_join, ev_h2d[0], ev_h2d[1], ev_comp[0], ev_comp[1], ev_d2h[0], ev_d2h[1]})
+fmcw_ctx::~fmcw_ctx() {
+  for (ncclComm_t m : comms) (void)rccl().comm_destroy(m);
+  for (fmcw_ctx* q : peers) delete q;
+  (void)hipSetDevice(device);
+  if (stream) (void)hipStreamSynchronize(stream);
+  for (auto& pd : pending) { (void)hipEventDestroy(pd.a); (void)hipEventDestroy(pd.b); }
+  for (auto e : pool) (void)hipEventDestroy(e);
+  for (int i = 0; i < kSlots; ++i)
+    for (hipEvent_t e : {ev_k1[i], ev_k2[i], ev_k3[i]})
       if (e) (void)hipEventDestroy(e);
-    for (hipStream_t x : {sd, sx, cin, cout})
-      if (x) { (void)hipStreamSynchronize(x); (void)hipStreamDestroy(x); }
-    if (stream) (void)hipStreamDestroy(stream);
-  }
+  for (hipEvent_t e : {ev_fork, ev_join, ev_h2d[0], ev_h2d[1], ev_comp[0], ev_comp[1], ev_d2h[0], ev_d2h[1]})
+    if (e) (void)hipEventDestroy(e);
+  for (hipStream_t x : {sd, sx, cin, cout})
+    if (x) { (void)hipStreamSynchronize(x); (void)hipStreamDestroy(x); }
+  if (stream) (void)hipStreamDestroy(stream);
+}
 
-  hipEvent_t get_event() {
-    if (!pool.empty()) {
-      hipEvent_t e = pool.back();
-      pool.pop_back();
-      return e;
-    }
-    hipEvent_t e = nullptr;
-    if (hipEventCreateWithFlags(&e, fmcw::kEvDevice) != hipSuccess) return nullptr;   // timing pairs
-    return e;
+// a table the caller rewrites (any nfft): the entry no longer holds what a cached nfft-64 key
+// says it holds, so the key is cleared (a later stft_tab64 with the same window rebuilds)
+float2* fmcw_ctx::stft_tab(hipStream_t st, size_t bytes, int* status) {
+  float2* t = static_cast<float2*>(s_tabs.get(st, bytes + STFT_TAPS_BYTES, status));
+  if (t) {
+    s_tabs.last->key = nullptr;
+    s_tabs.last->key_n = 0;
   }
-};
+  return t;
+}
+
+// The device calls at nfft 64 (the bench's config-4 STFT, two passes per step) keep the
+// stream's table while the window pointer and nfft are unchanged: k_stft64m compares the 20
+// taps stored behind the table with the call's window and forms its W entries itself when they
+// differ (a window rewritten in place), so the table is rebuilt once, not every pass.
+// *build: the caller must launch k_stft_table into the returned table.
+float2* fmcw_ctx::stft_tab64(hipStream_t st, const float* d_win, int nfft, bool* build, int* status) {
+  float2* t = static_cast<float2*>(s_tabs.get(st, (size_t)(nfft / 2 + 1) * 20 * 8 + STFT_TAPS_BYTES, status));
+  if (!t) return nullptr;
+  PerStream::Entry* e = s_tabs.last;
+  *build = !(e->key == d_win && e->key_n == nfft);
+  e->key = d_win;
+  e->key_n = nfft;
+  return t;
+}
 
 namespace {
-
-// Record an event pair around one launch when timing is enabled.
-struct StageTimer {
-  fmcw_ctx* c;
-  int stage;
-  hipStream_t s;
-  hipEvent_t a = nullptr;
-  StageTimer(fmcw_ctx* c_, int st, hipStream_t s_, int level = 1) : c(c_), stage(st), s(s_) {
-    // level 3: only the dominant kernels' launches (k_rdx, stage 8; K1 range-only, stage 6):
-    // every event pair on the stream costs the step a few microseconds
-    const bool on = c->timing == 3 ? (st == 6 || st == 8) : c->timing >= level;
-    if (on) {
-      a = c->get_event();
-      if (a) (void)hipEventRecord(a, s);
-    }
-  }
-  void done() {
-    if (a) {
-      hipEvent_t b = c->get_event();
-      if (b) {
-        (void)hipEventRecord(b, s);
-        c->pending.push_back({a, b, stage});
-      }
-      a = nullptr;
-    }
-  }
-};
-
-int set_device(fmcw_ctx* c) {
-  HIPCHK(hipSetDevice(c->device));
-  return FMCW_OK;
-}
 
 int check_params(const fmcw_params* p) {
   if (!p) return fail(FMCW_E_ARG, "params is NULL");
@@ -500,7 +191,6 @@ int range_cpt(int nr, int64_t nchirps) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(8, c));
 }
 
-hipStream_t pick(fmcw_ctx* c, void* stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream; }
 
 }  // namespace
 
@@ -1052,36 +742,6 @@ static int process_onepass(fmcw_ctx* c, const fmcw_params* p, const void* d_iq, 
 static int process_device_impl(fmcw_ctx* c, const fmcw_params* p, const void* d_iq, int32_t in_dtype, int64_t F,
                                float* d_prof, int32_t* d_count, int32_t* d_ridx, float* d_rmag, int32_t* d_didx,
                                float* d_slow, void* d_cube, void* d_rd, int32_t out_dtype, int64_t probe_column,
-                               float* d_probe, const SlowLeg* leg, void* stream);
-
-int fmcw_process_device(fmcw_ctx* c, const fmcw_params* p, const void* d_iq, int32_t in_dtype, int64_t F,
-                        float* d_prof, int32_t* d_count, int32_t* d_ridx, float* d_rmag, int32_t* d_didx,
-                        float* d_slow, void* d_cube, void* d_rd, int32_t out_dtype, int64_t probe_column,
-                        float* d_probe, void* stream) {
-  return process_device_impl(c, p, d_iq, in_dtype, F, d_prof, d_count, d_ridx, d_rmag, d_didx, d_slow, d_cube, d_rd,
-                             out_dtype, probe_column, d_probe, nullptr, stream);
-}
-
-int fmcw_process_slow_device(fmcw_ctx* c, const fmcw_params* p, const void* d_iq, int32_t in_dtype, int64_t F,
-                             float* d_prof, int32_t* d_count, int32_t* d_ridx, float* d_rmag, int32_t* d_didx,
-                             float* d_slow, void* d_rd, int32_t out_dtype, int32_t* d_frame_list, int64_t* d_len,
-                             float* d_pmax, void* stream) {
-  if (!d_frame_list || !d_len) return fail(FMCW_E_ARG, "d_frame_list / d_len is NULL");
-  if (F == 0 && c) {   // nothing to detect: the leg still starts (L = 0, max(P) = 0)
-    CHK(check_ctx(c, p));
-    hipStream_t s = pick(c, stream);
-    HIPCHK(hipMemsetAsync(d_len, 0, 8, s));
-    if (d_pmax) HIPCHK(hipMemsetAsync(d_pmax, 0, 4, s));
-    return FMCW_OK;
-  }
-  const SlowLeg leg{d_frame_list, d_len, d_pmax};
-  return process_device_impl(c, p, d_iq, in_dtype, F, d_prof, d_count, d_ridx, d_rmag, d_didx, d_slow, nullptr, d_rd,
-                             out_dtype, 0, nullptr, &leg, stream);
-}
-
-static int process_device_impl(fmcw_ctx* c, const fmcw_params* p, const void* d_iq, int32_t in_dtype, int64_t F,
-                               float* d_prof, int32_t* d_count, int32_t* d_ridx, float* d_rmag, int32_t* d_didx,
-                               float* d_slow, void* d_cube, void* d_rd, int32_t out_dtype, int64_t probe_column,
                                float* d_probe, const SlowLeg* leg, void* stream) {
   CHK(check_ctx(c, p));
   if (F < 0) return fail(FMCW_E_ARG, "F < 0");
@@ -1236,6 +896,31 @@ static int process_device_impl(fmcw_ctx* c, const fmcw_params* p, const void* d_
   return FMCW_OK;
 }
 
+int fmcw_process_device(fmcw_ctx* c, const fmcw_params* p, const void* d_iq, int32_t in_dtype, int64_t F,
+                        float* d_prof, int32_t* d_count, int32_t* d_ridx, float* d_rmag, int32_t* d_didx,
+                        float* d_slow, void* d_cube, void* d_rd, int32_t out_dtype, int64_t probe_column,
+                        float* d_probe, void* stream) {
+  return process_device_impl(c, p, d_iq, in_dtype, F, d_prof, d_count, d_ridx, d_rmag, d_didx, d_slow, d_cube, d_rd,
+                             out_dtype, probe_column, d_probe, nullptr, stream);
+}
+
+int fmcw_process_slow_device(fmcw_ctx* c, const fmcw_params* p, const void* d_iq, int32_t in_dtype, int64_t F,
+                             float* d_prof, int32_t* d_count, int32_t* d_ridx, float* d_rmag, int32_t* d_didx,
+                             float* d_slow, void* d_rd, int32_t out_dtype, int32_t* d_frame_list, int64_t* d_len,
+                             float* d_pmax, void* stream) {
+  if (!d_frame_list || !d_len) return fail(FMCW_E_ARG, "d_frame_list / d_len is NULL");
+  if (F == 0 && c) {   // nothing to detect: the leg still starts (L = 0, max(P) = 0)
+    CHK(check_ctx(c, p));
+    hipStream_t s = pick(c, stream);
+    HIPCHK(hipMemsetAsync(d_len, 0, 8, s));
+    if (d_pmax) HIPCHK(hipMemsetAsync(d_pmax, 0, 4, s));
+    return FMCW_OK;
+  }
+  const SlowLeg leg{d_frame_list, d_len, d_pmax};
+  return process_device_impl(c, p, d_iq, in_dtype, F, d_prof, d_count, d_ridx, d_rmag, d_didx, d_slow, nullptr, d_rd,
+                             out_dtype, 0, nullptr, &leg, stream);
+}
+
 int fmcw_range_fft_device(fmcw_ctx* c, const fmcw_params* p, const void* d_iq, int32_t in_dtype, int64_t F,
                           void* d_cube, int32_t out_dtype, float* d_prof, void* stream) {
   CHK(check_ctx(c, p));
@@ -1281,7 +966,7 @@ int fmcw_range_fft_device(fmcw_ctx* c, const fmcw_params* p, const void* d_iq, i
 }
 
 // ---------------------------------------------------------------------------
-// slow time + STFT
+// slow time (the STFT on it: api_stft.cpp)
 // ---------------------------------------------------------------------------
 int fmcw_compact_device(fmcw_ctx* c, const int32_t* d_count, int64_t F, int32_t pn, int32_t* d_list,
                         int64_t* d_len, void* stream) {
@@ -1296,528 +981,10 @@ int fmcw_compact_device(fmcw_ctx* c, const int32_t* d_count, int64_t F, int32_t 
   return FMCW_OK;
 }
 
-static int check_stft_shape(int32_t wlen, int32_t noverlap, int32_t nfft) {
-  if (wlen < 1 || wlen > 256) return fail(FMCW_E_ARG, "wlen must be in [1, 256]");
-  if (noverlap < 0 || noverlap >= wlen) return fail(FMCW_E_ARG, "noverlap must be in [0, wlen)");
-  if (nfft < wlen || (nfft % 2) != 0) return fail(FMCW_E_ARG, "nfft must be even and >= wlen");
-  return FMCW_OK;
-}
-
-int fmcw_stft_power_device(fmcw_ctx* c, const float* d_slow, const int32_t* d_list, const int64_t* d_len,
-                           int32_t pn, const float* d_halo, int32_t n_halo, const int64_t* d_halo_len,
-                           const float* d_win, int32_t wlen,
-                           int32_t noverlap, int32_t nfft, double fs, int64_t max_seg, float* d_P, float* d_pmax,
-                           int64_t* d_nseg, void* stream) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  CHK(check_stft_shape(wlen, noverlap, nfft));
-  if (pn < 1 || n_halo < 0 || max_seg < 0 || !(fs > 0)) return fail(FMCW_E_ARG, "bad pn / n_halo / max_seg / fs");
-  if (!d_slow || !d_list || !d_len || !d_win || !d_pmax || !d_nseg || (n_halo > 0 && !d_halo))
-    return fail(FMCW_E_ARG, "NULL device pointer");   // d_P may be NULL: max(P) only
-  // the shard split of the slow-time signal (dist.py) starts every shard's segment grid at its own
-  // sample 0 and takes wlen-1 samples of right halo: that is the global grid only for hop 1
-  if (n_halo > 0 && wlen - noverlap != 1)
-    return fail(FMCW_E_ARG, "a halo (sharded STFT) needs hop 1, i.e. noverlap = wlen - 1");
-  CHK(set_device(c));
-  hipStream_t s = pick(c, stream);
-  fmcw::StftArgs a{};
-  a.slow_mag = d_slow; a.frame_list = d_list; a.len = d_len; a.pn = pn;
-  a.halo = d_halo; a.n_halo = n_halo; a.halo_len = d_halo_len;
-  a.win = d_win; a.wlen = wlen; a.hop = wlen - noverlap; a.nfft = nfft;
-  a.inv_fs = (float)(1.0 / fs);
-  a.max_seg = max_seg; a.P = d_P; a.pmax = d_pmax; a.nseg_out = d_nseg;
-  StageTimer tm(c, 4, s);
-  if (fmcw::stft_fast_path(wlen, a.hop)) {        // the reference's 20-tap window: W table + k_stft20
-    int st = FMCW_OK;
-    bool build = true;
-    // the cached nfft-64 table only for the forms that tolerate a stale one; the table form (any other nfft,
-    // an unaligned d_P, FMCW_STFT_MFMA=0) gets a table built from this call's window (stft_tab clears the key)
-    const int mode = d_P ? 0 : 1;
-    float2* tab = fmcw::stft_form(a, mode, nullptr) != fmcw::STFT_FORM_TABLE
-                      ? c->stft_tab64(s, d_win, nfft, &build, &st)
-                      : c->stft_tab(s, (size_t)(nfft / 2 + 1) * 20 * 8, &st);
-    CHK(st);
-    if (build) HIPCHK(fmcw::launch_stft_table(d_win, nfft, tab, s));
-    // device API: d_P is the caller's [max_seg][nfft/2+1] (fmcw.h), the table this stream's
-    HIPCHK(fmcw::launch_stft20(a, tab, mode, nullptr, s, max_seg * (int64_t)(nfft / 2 + 1),
-                               (int64_t)(nfft / 2 + 1) * 20));
-    CHK(c->stft_tab_done(s));
-  } else {
-    HIPCHK(fmcw::launch_stft_power(a, s));
-  }
-  tm.done();
-  return FMCW_OK;
-}
-
-int fmcw_stft_db_direct_device(fmcw_ctx* c, const float* d_slow, const int32_t* d_list, const int64_t* d_len,
-                               int32_t pn, const float* d_halo, int32_t n_halo, const int64_t* d_halo_len,
-                               const float* d_win, int32_t wlen, int32_t noverlap, int32_t nfft, double fs,
-                               int64_t max_seg, const float* d_pmax, float* d_out, void* stream) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  CHK(check_stft_shape(wlen, noverlap, nfft));
-  if (pn < 1 || n_halo < 0 || max_seg < 0 || !(fs > 0)) return fail(FMCW_E_ARG, "bad pn / n_halo / max_seg / fs");
-  if (!d_slow || !d_list || !d_len || !d_win || !d_pmax || !d_out || (n_halo > 0 && !d_halo))
-    return fail(FMCW_E_ARG, "NULL device pointer");
-  if (!fmcw::stft_fast_path(wlen, wlen - noverlap))
-    return fail(FMCW_E_ARG, "the direct dB STFT needs the 20-tap window and hop <= 4");
-  if (n_halo > 0 && wlen - noverlap != 1)
-    return fail(FMCW_E_ARG, "a halo (sharded STFT) needs hop 1, i.e. noverlap = wlen - 1");
-  CHK(set_device(c));
-  hipStream_t s = pick(c, stream);
-  fmcw::StftArgs a{};
-  a.slow_mag = d_slow; a.frame_list = d_list; a.len = d_len; a.pn = pn;
-  a.halo = d_halo; a.n_halo = n_halo; a.halo_len = d_halo_len;
-  a.win = d_win; a.wlen = wlen; a.hop = wlen - noverlap; a.nfft = nfft;
-  a.inv_fs = (float)(1.0 / fs);
-  a.max_seg = max_seg; a.P = nullptr; a.pmax = const_cast<float*>(d_pmax); a.nseg_out = nullptr;
-  StageTimer tm(c, 5, s);
-  int st = FMCW_OK;
-  bool build = true;
-  // as fmcw_stft_power_device: an unaligned d_out takes the table form, which must not see a cached table
-  float2* tab = fmcw::stft_form(a, 2, d_out) != fmcw::STFT_FORM_TABLE
-                    ? c->stft_tab64(s, d_win, nfft, &build, &st)
-                    : c->stft_tab(s, (size_t)(nfft / 2 + 1) * 20 * 8, &st);
-  CHK(st);
-  if (build) HIPCHK(fmcw::launch_stft_table(d_win, nfft, tab, s));
-  HIPCHK(fmcw::launch_stft20(a, tab, 2, d_out, s, max_seg * (int64_t)(nfft / 2 + 1), (int64_t)(nfft / 2 + 1) * 20));
-  CHK(c->stft_tab_done(s));
-  tm.done();
-  return FMCW_OK;
-}
-
-// logspace(log10(fs/nfft), log10(fs/2), n) located on F = (0:nfft/2)*fs/nfft
-static void log_table(int nfft, double fs, int n, std::vector<int32_t>& idx, std::vector<float>& wt,
-                      std::vector<double>* fq_out) {
-  const int nb = nfft / 2 + 1;
-  const double df = fs / nfft;
-  const double a = std::log10(df), b = std::log10((nb - 1) * df);
-  idx.resize(n);
-  wt.resize(n);
-  if (fq_out) fq_out->resize(n);
-  for (int j = 0; j < n; ++j) {
-    const double e = (n == 1) ? b : (j == n - 1 ? b : a + j * (b - a) / (n - 1));
-    const double fq = std::pow(10.0, e);
-    int i0 = (int)std::floor(fq / df);
-    if (i0 < 0) i0 = 0;
-    if (i0 > nb - 2) i0 = nb - 2;
-    idx[j] = i0;
-    wt[j] = (float)((fq - i0 * df) / df);
-    if (fq_out) (*fq_out)[j] = fq;
-  }
-}
-
-int fmcw_stft_db_device(fmcw_ctx* c, const float* d_P, const int64_t* d_nseg, int64_t max_seg, int32_t nfft,
-                        double fs, const float* d_pmax, int32_t n_log_bins, float* d_out, void* stream) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  if (nfft < 2 || (nfft % 2) != 0 || n_log_bins < 0 || max_seg < 0 || !(fs > 0))
-    return fail(FMCW_E_ARG, "bad nfft / n_log_bins / max_seg / fs");
-  if (!d_P || !d_nseg || !d_pmax || !d_out) return fail(FMCW_E_ARG, "NULL device pointer");
-  if (n_log_bins > 0 && d_out == d_P) return fail(FMCW_E_ARG, "d_out may alias d_P only without resampling");
-  CHK(set_device(c));
-  hipStream_t s = pick(c, stream);
-  if (n_log_bins > 0) {
-    std::vector<int32_t> idx;
-    std::vector<float> wt;
-    log_table(nfft, fs, n_log_bins, idx, wt, nullptr);
-    CHK(c->s_lidx.ensure(idx.size() * 4));
-    CHK(c->s_lw.ensure(wt.size() * 4));
-    HIPCHK(hipMemcpyAsync(c->s_lidx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->s_lw.p, wt.data(), wt.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));   // host vectors go out of scope
-  }
-  fmcw::StftDbArgs a{};
-  a.P = d_P; a.nseg = d_nseg; a.max_seg = max_seg; a.nbins_in = nfft / 2 + 1;
-  a.pmax = d_pmax; a.nlog = n_log_bins;
-  a.lidx = n_log_bins > 0 ? c->s_lidx.as<int32_t>() : nullptr;
-  a.lw = n_log_bins > 0 ? c->s_lw.as<float>() : nullptr;
-  a.out = d_out;
-  StageTimer tm(c, 5, s);
-  HIPCHK(fmcw::launch_stft_db(a, s));
-  tm.done();
-  return FMCW_OK;
-}
-
-int fmcw_stft_sizes(int64_t L, int32_t wlen, int32_t noverlap, int32_t nfft, int32_t n_log_bins, int64_t* nseg,
-                    int32_t* nfft_used, int32_t* nbins_out) {
-  if (L < 0 || n_log_bins < 0) return fail(FMCW_E_ARG, "L < 0 or n_log_bins < 0");
-  int32_t nf = nfft;
-  if (nf == 0) {                       // :273 nfft_stft = 2^nextpow2(length(iq_data(:)))
-    int64_t v = 1;
-    while (v < L) v <<= 1;
-    if (v > (1 << 26)) return fail(FMCW_E_ARG, "2^nextpow2(L) too large");
-    nf = (int32_t)v;
-  }
-  if (wlen < 1 || noverlap < 0 || noverlap >= wlen) return fail(FMCW_E_ARG, "need 0 <= noverlap < wlen");
-  const int hop = wlen - noverlap;
-  const int64_t ns = (L - noverlap) >= 0 ? (L - noverlap) / hop : 0;   // fix((nx-noverlap)/(nwind-noverlap))
-  if (nseg) *nseg = ns;
-  if (nfft_used) *nfft_used = nf;
-  if (nbins_out) *nbins_out = n_log_bins > 0 ? n_log_bins : nf / 2 + 1;
-  if (ns < 1) return fail(FMCW_E_DATA, "spectrogram: signal length " + std::to_string(L) + " is shorter than the window");
-  CHK(check_stft_shape(wlen, noverlap, nf));
-  return FMCW_OK;
-}
-
-int fmcw_render_spectrogram_device(fmcw_ctx* c, const float* d_Q, int32_t nq, const int64_t* d_nseg,
-                                   const float* d_pmax, int32_t nfft, double fs, double t0, double dt, int32_t width,
-                                   int32_t height, uint8_t* d_img, void* stream) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  if (!d_Q || !d_nseg || !d_pmax || !d_img) return fail(FMCW_E_ARG, "NULL device pointer");
-  if (nfft < 2 || (nfft % 2) != 0 || nq < 1 || nq > nfft / 2 || !(fs > 0) || !(dt > 0))
-    return fail(FMCW_E_ARG, "bad nfft / nq / fs / dt");
-  if (width < 1 || height < 1 || width > 65536 || height > 65535) return fail(FMCW_E_ARG, "bad image size");
-  CHK(set_device(c));
-  fmcw::RenderArgs a{};
-  a.Q = d_Q; a.nq = nq; a.nseg = d_nseg; a.pmax = d_pmax;
-  a.nb = nfft / 2 + 1; a.nfft = nfft; a.seam = a.nb - a.nb / 2 - 1;
-  a.fs = fs; a.t0 = t0; a.dt = dt;
-  a.fmax = FMCW_PNG_FMAX_HZ; a.cmin = FMCW_PNG_CMIN_DB; a.cmax = FMCW_PNG_CMAX_DB;
-  a.W = width; a.H = height; a.img = d_img;
-  hipStream_t s = pick(c, stream);
-  StageTimer tm(c, 9, s);
-  HIPCHK(fmcw::launch_render(a, s));
-  tm.done();
-  return FMCW_OK;
-}
-
-static int stft_impl(fmcw_ctx* c, const float* x, int64_t L, const float* win, int32_t wlen, int32_t noverlap,
-                     int32_t nfft, double fs, int32_t n_log_bins, float* T, float* freq, float* intensity,
-                     const char* png_path, int32_t width, int32_t height, int64_t* png_bytes);
-
-int fmcw_stft(fmcw_ctx* c, const float* x, int64_t L, const float* win, int32_t wlen, int32_t noverlap, int32_t nfft,
-              double fs, int32_t n_log_bins, float* T, float* freq, float* intensity) {
-  return stft_impl(c, x, L, win, wlen, noverlap, nfft, fs, n_log_bins, T, freq, intensity, nullptr, 0, 0, nullptr);
-}
-
-int fmcw_stft_png(fmcw_ctx* c, const float* x, int64_t L, const float* win, int32_t wlen, int32_t noverlap,
-                  int32_t nfft, double fs, int32_t n_log_bins, float* T, float* freq, float* intensity,
-                  const char* png_path, int32_t width, int32_t height, int64_t* png_bytes) {
-  if (!png_path) return fail(FMCW_E_ARG, "png_path is NULL");
-  return stft_impl(c, x, L, win, wlen, noverlap, nfft, fs, n_log_bins, T, freq, intensity, png_path,
-                   width > 0 ? width : FMCW_PNG_DEFAULT_W, height > 0 ? height : FMCW_PNG_DEFAULT_H, png_bytes);
-}
-
-// A large device -> pageable-host copy on stream s, through the two pinned out slots of the
-// context: the DMA of piece i overlaps the host threads copying piece i-1 to the caller (and
-// taking its first-touch page faults in parallel). Returns once dst holds every byte.
-static int d2h_big(fmcw_ctx* c, void* dst, const void* d_src, size_t bytes, hipStream_t s) {
-  constexpr size_t kPiece = 32u << 20;
-  if (bytes < 2 * kPiece) {
-    HIPCHK(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return FMCW_OK;
-  }
-  CHK(c->pin_out.ensure(2 * kPiece));
-  const size_t n = (bytes + kPiece - 1) / kPiece;
-  auto piece = [&](size_t i) { return std::min(kPiece, bytes - i * kPiece); };
-  for (size_t i = 0; i <= n; ++i) {
-    if (i < n) {
-      const int b = (int)(i & 1);
-      HIPCHK(hipMemcpyAsync(c->pin_out.at(b * kPiece), static_cast<const char*>(d_src) + i * kPiece, piece(i),
-                            hipMemcpyDeviceToHost, s));
-      HIPCHK(hipEventRecord(c->ev_d2h[b], s));
-    }
-    if (i >= 1) {   // piece i-1 is in its pinned slot once its event fires; slot (i-1)&1 is reused by piece i+1
-      const int b = (int)((i - 1) & 1);
-      HIPCHK(hipEventSynchronize(c->ev_d2h[b]));
-      par_memcpy(static_cast<char*>(dst) + (i - 1) * kPiece, c->pin_out.at(b * kPiece), piece(i - 1));
-    }
-  }
-  return FMCW_OK;
-}
-
-// max(P) of :282-283 over every bin of a large nfft without evaluating every bin of every segment.
-// |X_s(w)| of a 20-tap segment is a trigonometric polynomial of degree 19, so (Bernstein) within one
-// coarse step h = 2 pi / K of its peak it is at least (1 - 19 h) of the peak.  Pass 1 takes each
-// segment's max over the coarse bins k = m nfft / K (exact P values of the fine grid, so their
-// maximum G is a lower bound of max(P)); a segment whose coarse max is below G (1 - 19 h)^2 cannot
-// hold max(P).  Pass 2 takes the max over every bin of the 256-segment tiles that hold a
-// candidate: the same P values the full pass would compare, so the result is the same bits.
-static int stft_coarse_max(fmcw_ctx* d, const fmcw::StftArgs& a0, hipStream_t s) {
-  // The bound below holds for the 20-tap window only (a degree-19 trigonometric polynomial per
-  // segment; any sign of the samples) and for a power-of-two nfft of at least 2^16, so that the
-  // coarse grid (every D-th bin) holds DC, Nyquist and an interior bin within h of any peak.
-  if (!fmcw::stft_fast_path(a0.wlen, a0.hop)) return fail(FMCW_E_ARG, "stft_coarse_max: not the 20-tap fast path");
-  if (a0.nfft < (1 << 16) || (a0.nfft & (a0.nfft - 1))) return fail(FMCW_E_ARG, "stft_coarse_max: nfft must be a power of two >= 2^16");
-  const int nf = a0.nfft, K = std::min(16384, nf / 8), D = nf / K, nc = K / 2 + 1;   // nf >= 2^16
-  const int64_t ns = a0.max_seg;
-  if (ns < 1 || ns > 0x7fffffffLL) return fail(FMCW_E_ARG, "stft_coarse_max: bad segment count");
-  std::vector<int32_t> cb(nc);
-  for (int m = 0; m < nc; ++m) cb[m] = D * m;
-  CHK(d->s_cbins.ensure((size_t)nc * 4));
-  CHK(d->s_segmax.ensure((size_t)ns * 4));
-  int st = FMCW_OK;
-  float2* tab = d->stft_tab(s, (size_t)(nf / 2 + 1) * 20 * 8, &st);
-  CHK(st);
-  HIPCHK(hipMemcpyAsync(d->s_cbins.p, cb.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(fmcw::launch_stft_table(a0.win, nf, tab, s));
-  fmcw::StftArgs a = a0;
-  a.bins = d->s_cbins.as<int32_t>();
-  a.ncol = nc;
-  // mode 4 writes one float per segment: s_segmax holds ns (launch_stft20 checks the capacity)
-  HIPCHK(fmcw::launch_stft20(a, tab, 4, d->s_segmax.as<float>(), s, (int64_t)(d->s_segmax.n / 4),
-                             (int64_t)(nf / 2 + 1) * 20));
-  std::vector<float> sm((size_t)ns);
-  HIPCHK(hipMemcpyAsync(sm.data(), d->s_segmax.p, (size_t)ns * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  float G = 0.f;
-  for (float v : sm) G = std::max(G, v);
-  const double f = 1.0 - (double)(a0.wlen - 1) * 2.0 * M_PI / K;   // degree wlen - 1 (the 20-tap fast path)
-  const float thr = (float)((double)G * f * f * (1.0 - 1e-3));   // margin for the fp32 rounding of P
-  std::vector<int32_t> tiles;
-  for (int64_t t = 0; t * 256 < ns; ++t) {
-    const int64_t e = std::min<int64_t>(ns, (t + 1) * 256);
-    for (int64_t i = t * 256; i < e; ++i)
-      if (sm[(size_t)i] >= thr) { tiles.push_back((int32_t)t); break; }
-  }
-  CHK(d->s_tiles.ensure(tiles.size() * 4));
-  HIPCHK(hipMemcpyAsync(d->s_tiles.p, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice, s));
-  a = a0;
-  a.tiles = d->s_tiles.as<int32_t>();
-  a.ntiles = (int)tiles.size();
-  HIPCHK(fmcw::launch_stft20(a, tab, 1, nullptr, s, 0, (int64_t)(nf / 2 + 1) * 20));
-  CHK(d->stft_tab_done(s));
-  HIPCHK(hipStreamSynchronize(s));   // tiles / cb leave scope
-  d->last_coarse_tiles = (int64_t)tiles.size();
-  if (const char* e = std::getenv("FMCW_STFT_DEBUG"); e && e[0] == '1')
-    std::fprintf(stderr, "stft_coarse_max: nfft %d, %lld segments, %zu of %lld tiles in full\n", nf, (long long)ns,
-                 tiles.size(), (long long)((ns + 255) / 256));
-  return FMCW_OK;
-}
-
-static int stft_impl(fmcw_ctx* c, const float* x, int64_t L, const float* win, int32_t wlen, int32_t noverlap,
-                     int32_t nfft, double fs, int32_t n_log_bins, float* T, float* freq, float* intensity,
-                     const char* png_path, int32_t width, int32_t height, int64_t* png_bytes) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  if ((!x && L > 0) || !win || !T || !freq || !intensity) return fail(FMCW_E_ARG, "NULL pointer");
-  if (!(fs > 0)) return fail(FMCW_E_ARG, "fs must be > 0");
-  if (L > 0x7fffffffLL) return fail(FMCW_E_ARG, "L too large for the host API");
-  int64_t nseg = 0;
-  int32_t nf = 0, nbo = 0;
-  CHK(fmcw_stft_sizes(L, wlen, noverlap, nfft, n_log_bins, &nseg, &nf, &nbo));   // nfft rule on the whole signal
-  const int hop = wlen - noverlap;
-  const int nb = nf / 2 + 1;
-  const int world = 1 + (int)c->peers.size();
-  auto dev = [&](int g) { return g == 0 ? c : c->peers[g - 1]; };
-  const double df = fs / nf;
-  const int nq = png_path ? (int)std::min<int64_t>(nb - 1, (int64_t)std::floor(FMCW_PNG_FMAX_HZ / df) + 2) : 0;
-  // With the log-frequency output (:286-299) and the 20-tap window, P is formed only for the
-  // bins interp1 and the picture read: a max(P)-only pass over every bin, then those columns
-  // ([seg][ncolP], ascending bins). Otherwise every bin ([seg][nb]).
-  const bool sel_mode = n_log_bins > 0 && fmcw::stft_fast_path(wlen, hop);
-  std::vector<int32_t> bins, lidx;
-  std::vector<float> lw;
-  if (sel_mode) {
-    log_table(nf, fs, n_log_bins, lidx, lw, nullptr);
-    std::vector<int32_t> pos(nb, 0);
-    for (int32_t i0 : lidx) pos[i0] = pos[i0 + 1] = 1;
-    for (int k = 0; k < nq; ++k) pos[k] = 1;
-    if (png_path) pos[nb - 1] = 1;
-    for (int k = 0; k < nb; ++k)
-      if (pos[k]) { pos[k] = (int32_t)bins.size(); bins.push_back(k); }
-    for (auto& i0 : lidx) i0 = pos[i0];   // i0 and i0+1 are both listed, so they are adjacent columns
-  }
-  const int ncolP = sel_mode ? (int)bins.size() : nb;
-  // per device, the call's inputs (its samples, the one-entry frame list, the length, the window,
-  // the listed bins and the interp1 table) in one arena: one pinned H2D copy instead of seven
-  struct InOff { size_t x, list, len, win, bins, lidx, lw; };
-  std::vector<InOff> io(world);
-  // Segments are sharded contiguously over the devices; device g takes the
-  // samples its segments cover (its halo is simply the next samples of x).
-  // 1) P and the local max(P) per device
-  for (int g = 0; g < world; ++g) {
-    fmcw_ctx* d = dev(g);
-    int64_t s0, ns;
-    shard(nseg, g, world, s0, ns);
-    CHK(set_device(d));
-    hipStream_t s = d->stream;
-    const int64_t Ld = ns > 0 ? (ns - 1) * hop + wlen : 0;
-    CHK(d->s_P.ensure((size_t)std::max<int64_t>(ns, 1) * ncolP * 4));
-    CHK(d->s_pmax.ensure(4));
-    CHK(d->s_nseg.ensure(8));
-    CHK(d->s_out.ensure((size_t)std::max<int64_t>(ns, 1) * nbo * 4));
-    HIPCHK(hipMemsetAsync(d->s_pmax.p, 0, 4, s));
-    if (ns == 0) continue;
-    Arena ar;
-    InOff& o = io[g];
-    o.x = ar.add((size_t)Ld * 4); o.list = ar.add(4); o.len = ar.add(8); o.win = ar.add((size_t)wlen * 4);
-    o.bins = ar.add(bins.size() * 4); o.lidx = ar.add(lidx.size() * 4); o.lw = ar.add(lw.size() * 4);
-    CHK(d->s_in.ensure(ar.off));
-    CHK(d->pin_sin.ensure(ar.off));
-    {
-      char* h = d->pin_sin.at(0);
-      par_memcpy(h + o.x, x + s0 * hop, (size_t)Ld * 4);
-      const int32_t zero = 0;
-      std::memcpy(h + o.list, &zero, 4);
-      std::memcpy(h + o.len, &Ld, 8);
-      std::memcpy(h + o.win, win, (size_t)wlen * 4);
-      if (!bins.empty()) std::memcpy(h + o.bins, bins.data(), bins.size() * 4);
-      if (!lidx.empty()) std::memcpy(h + o.lidx, lidx.data(), lidx.size() * 4);
-      if (!lw.empty()) std::memcpy(h + o.lw, lw.data(), lw.size() * 4);
-    }
-    HIPCHK(hipMemcpyAsync(d->s_in.p, d->pin_sin.p, ar.off, hipMemcpyHostToDevice, s));
-    char* const di = d->s_in.as<char>();
-    float* const d_x = reinterpret_cast<float*>(di + o.x);
-    int32_t* const d_list = reinterpret_cast<int32_t*>(di + o.list);
-    int64_t* const d_len = reinterpret_cast<int64_t*>(di + o.len);
-    float* const d_win = reinterpret_cast<float*>(di + o.win);
-    // the shard's samples are one "frame" of Ld samples in the compaction indirection
-    const char* ce = std::getenv("FMCW_STFT_COARSE");   // 0: every bin of every segment (tests, A/B)
-    const char* me = std::getenv("FMCW_STFT_MFMA");
-    const bool coarse_ok = !(ce && ce[0] == '0') && !(me && me[0] == '0');
-    if (sel_mode && coarse_ok && nf >= (1 << 16)) {   // max(P) only, over a large nfft: coarse-to-fine
-      fmcw::StftArgs a{};
-      a.slow_mag = d_x; a.frame_list = d_list; a.len = d_len; a.pn = (int32_t)Ld;
-      a.win = d_win; a.wlen = wlen; a.hop = hop; a.nfft = nf; a.inv_fs = (float)(1.0 / fs);
-      a.max_seg = ns; a.P = nullptr; a.pmax = d->s_pmax.as<float>(); a.nseg_out = d->s_nseg.as<int64_t>();
-      StageTimer tm(d, 4, s);
-      CHK(stft_coarse_max(d, a, s));
-      tm.done();
-    } else if (sel_mode) {   // max(P) only, in the table form the listed-bins pass below uses (at nfft 64
-                             // too: P / max(P) of the listed bins then peaks at exactly 0 dB, as in MATLAB)
-      fmcw::StftArgs a{};
-      a.slow_mag = d_x; a.frame_list = d_list; a.len = d_len; a.pn = (int32_t)Ld;
-      a.win = d_win; a.wlen = wlen; a.hop = hop; a.nfft = nf; a.inv_fs = (float)(1.0 / fs);
-      a.max_seg = ns; a.P = nullptr; a.pmax = d->s_pmax.as<float>(); a.nseg_out = d->s_nseg.as<int64_t>();
-      a.table_form = 1;
-      StageTimer tm(d, 4, s);
-      int st = FMCW_OK;
-      float2* tab = d->stft_tab(s, (size_t)(nf / 2 + 1) * 20 * 8, &st);
-      CHK(st);
-      HIPCHK(fmcw::launch_stft_table(d_win, nf, tab, s));
-      HIPCHK(fmcw::launch_stft20(a, tab, 1, nullptr, s, 0, (int64_t)(nf / 2 + 1) * 20));
-      CHK(d->stft_tab_done(s));
-      tm.done();
-    } else {
-      CHK(fmcw_stft_power_device(d, d_x, d_list, d_len, (int32_t)Ld, nullptr, 0, nullptr, d_win, wlen, noverlap, nf, fs, ns,
-                                 d->s_P.as<float>(), d->s_pmax.as<float>(), d->s_nseg.as<int64_t>(), s));
-    }
-    if (sel_mode) {   // second pass: P of the listed bins (the W table the first pass built on s is reused)
-      fmcw::StftArgs a{};
-      a.slow_mag = d_x; a.frame_list = d_list; a.len = d_len;
-      a.pn = (int32_t)Ld; a.win = d_win; a.wlen = wlen; a.hop = hop; a.nfft = nf;
-      a.inv_fs = (float)(1.0 / fs); a.max_seg = ns; a.bins = reinterpret_cast<int32_t*>(di + o.bins); a.ncol = ncolP;
-      StageTimer tm(d, 4, s);
-      int st = FMCW_OK;
-      float2* tab = d->stft_tab(s, (size_t)(nf / 2 + 1) * 20 * 8, &st);   // the first pass's table on s (both
-      CHK(st);                                                             // first-pass forms built it for d_win)
-      HIPCHK(fmcw::launch_stft20(a, tab, 3, d->s_P.as<float>(), s, (int64_t)(d->s_P.n / 4), (int64_t)(nf / 2 + 1) * 20));
-      CHK(d->stft_tab_done(s));
-      tm.done();
-    }
-    if (world > 1) HIPCHK(hipStreamSynchronize(s));   // local max(P) final (step 2 may read it through the host)
-  }
-  // 2) the global max(P) of :282-283: RCCL all_reduce(max) across the devices
-  if (world > 1) {
-    if (!c->comms.empty()) {
-      NCCLCHK(rccl().group_start());
-      for (int g = 0; g < world; ++g) {
-        fmcw_ctx* d = dev(g);
-        CHK(set_device(d));
-        NCCLCHK(rccl().all_reduce(d->s_pmax.p, d->s_pmax.p, 1, ncclFloat32, ncclMax, c->comms[g], d->stream));
-      }
-      NCCLCHK(rccl().group_end());
-    } else {   // several contexts on ONE device (no communicator can span them): 4 bytes through the host
-      float m = 0.f;
-      for (int g = 0; g < world; ++g) {
-        float v = 0.f;
-        CHK(set_device(dev(g)));
-        HIPCHK(hipMemcpy(&v, dev(g)->s_pmax.p, 4, hipMemcpyDeviceToHost));
-        m = std::max(m, v);
-      }
-      for (int g = 0; g < world; ++g) {
-        CHK(set_device(dev(g)));
-        HIPCHK(hipMemcpy(dev(g)->s_pmax.p, &m, 4, hipMemcpyHostToDevice));
-      }
-    }
-  }
-  // 2b) spectrogram.png (:331-348) from the linear-bin P before it is overwritten:
-  //     the bins below ylim plus the Nyquist bin of every segment, gathered to device 0
-  std::vector<uint8_t> img;
-  if (png_path) {
-    std::vector<float> q((size_t)std::max<int64_t>(nseg, 1) * (nq + 1));
-    for (int g = 0; g < world; ++g) {
-      fmcw_ctx* d = dev(g);
-      int64_t s0, ns;
-      shard(nseg, g, world, s0, ns);
-      if (ns == 0) continue;
-      CHK(set_device(d));
-      // bins 0..nq-1 are the first nq columns of P and the Nyquist bin its last, in both layouts
-      HIPCHK(hipMemcpy2DAsync(q.data() + s0 * (nq + 1), (nq + 1) * 4, d->s_P.p, (size_t)ncolP * 4, (size_t)nq * 4, ns,
-                              hipMemcpyDeviceToHost, d->stream));
-      HIPCHK(hipMemcpy2DAsync(q.data() + s0 * (nq + 1) + nq, (nq + 1) * 4, d->s_P.as<float>() + (ncolP - 1),
-                              (size_t)ncolP * 4, 4, ns, hipMemcpyDeviceToHost, d->stream));
-    }
-    for (int g = 0; g < world; ++g) {
-      CHK(set_device(dev(g)));
-      HIPCHK(hipStreamSynchronize(dev(g)->stream));
-    }
-    CHK(set_device(c));
-    hipStream_t s = c->stream;
-    CHK(c->r_q.ensure(q.size() * 4));
-    CHK(c->r_nseg.ensure(8));
-    CHK(c->r_img.ensure((size_t)height * (width + 1)));
-    HIPCHK(hipMemcpyAsync(c->r_q.p, q.data(), q.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->r_nseg.p, &nseg, 8, hipMemcpyHostToDevice, s));
-    CHK(fmcw_render_spectrogram_device(c, c->r_q.as<float>(), nq, c->r_nseg.as<int64_t>(), c->s_pmax.as<float>(), nf, fs,
-                                       (wlen / 2.0) / fs, hop / fs, width, height, c->r_img.as<uint8_t>(), s));
-    img.resize((size_t)height * (width + 1));
-    HIPCHK(hipMemcpyAsync(img.data(), c->r_img.p, img.size(), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-  }
-  // 3) dB (+ log-frequency resampling) and the rows back into intensity
-  for (int g = 0; g < world; ++g) {
-    fmcw_ctx* d = dev(g);
-    int64_t s0, ns;
-    shard(nseg, g, world, s0, ns);
-    if (ns == 0) continue;
-    CHK(set_device(d));
-    hipStream_t s = d->stream;
-    if (sel_mode) {   // interp1 over the listed columns (lidx holds column positions; uploaded in step 1)
-      fmcw::StftDbArgs a{};
-      a.P = d->s_P.as<float>(); a.nseg = d->s_nseg.as<int64_t>(); a.max_seg = ns; a.nbins_in = ncolP;
-      a.pmax = d->s_pmax.as<float>(); a.nlog = n_log_bins;
-      a.lidx = reinterpret_cast<int32_t*>(d->s_in.as<char>() + io[g].lidx);
-      a.lw = reinterpret_cast<float*>(d->s_in.as<char>() + io[g].lw); a.out = d->s_out.as<float>();
-      StageTimer tm(d, 5, s);
-      HIPCHK(fmcw::launch_stft_db(a, s));
-      tm.done();
-    } else {
-      CHK(fmcw_stft_db_device(d, d->s_P.as<float>(), d->s_nseg.as<int64_t>(), ns, nf, fs, d->s_pmax.as<float>(),
-                              n_log_bins, n_log_bins > 0 ? d->s_out.as<float>() : d->s_P.as<float>(), s));
-    }
-    const float* res = n_log_bins > 0 ? d->s_out.as<float>() : d->s_P.as<float>();
-    CHK(d2h_big(d, intensity + s0 * nbo, res, (size_t)ns * nbo * 4, s));
-  }
-  for (int g = 0; g < world; ++g) {
-    CHK(set_device(dev(g)));
-    HIPCHK(hipStreamSynchronize(dev(g)->stream));
-  }
-  if (png_path) CHK(fmcw::png_write_indexed(png_path, img.data(), width, height, 1, 0, png_bytes));
-  for (int64_t i = 0; i < nseg; ++i) T[i] = (float)(((double)i * hop + wlen / 2.0) / fs);   // spectrogram T
-  if (n_log_bins > 0) {
-    std::vector<int32_t> idx;
-    std::vector<float> wt;
-    std::vector<double> fq;
-    log_table(nf, fs, n_log_bins, idx, wt, &fq);
-    for (int j = 0; j < n_log_bins; ++j) freq[j] = (float)fq[j];
-  } else {
-    for (int j = 0; j < nb; ++j) freq[j] = (float)(j * fs / nf);
-  }
-  return FMCW_OK;
-}
-
 // ---------------------------------------------------------------------------
 // host-pointer per-frame API
 // ---------------------------------------------------------------------------
 }  // extern "C"
-
-// Frames per host-path chunk: ~64 MiB of input per slot (FMCW_HOST_CHUNK
-// overrides, for tests of the chunk seams).
-static int64_t host_chunk(size_t frame_in_bytes, int64_t F) {
-  int64_t fc = (int64_t)((64ull << 20) / std::max<size_t>(frame_in_bytes, 1));
-  if (const char* e = std::getenv("FMCW_HOST_CHUNK"); e && std::atoll(e) > 0) fc = std::atoll(e);
-  return std::max<int64_t>(1, std::min<int64_t>(fc, F));
-}
 
 // The host-pointer calls as a two-slot pipeline over chunks of frames:
 //   host:  caller's iq chunk i -> pinned slot i%2 (once the H2D of chunk i-2 has left it)
@@ -1968,32 +1135,6 @@ static int range_fft_host_one(fmcw_ctx* c, const fmcw_params* p, const void* iq,
 
 }  // extern "C"
 
-// Run fn(device context, shard index, f0, n) on every device of the context,
-// one host thread per device (their H2D copies, kernels and D2H copies then
-// overlap), over contiguous shards of `total` items.  The first failing
-// device's status and message are returned.
-template <typename Fn>
-static int over_devices(fmcw_ctx* c, int64_t total, Fn&& fn) {
-  const int world = 1 + (int)c->peers.size();
-  if (world == 1) return fn(c, 0, (int64_t)0, total);
-  std::vector<int> st(world, FMCW_OK);
-  std::vector<std::string> msg(world);
-  std::vector<std::thread> th;
-  for (int g = 0; g < world; ++g) {
-    th.emplace_back([&, g] {
-      int64_t f0, n;
-      shard(total, g, world, f0, n);
-      fmcw_ctx* d = g == 0 ? c : c->peers[g - 1];
-      st[g] = n > 0 ? fn(d, g, f0, n) : FMCW_OK;
-      if (st[g] != FMCW_OK) msg[g] = g_err;
-    });
-  }
-  for (auto& t : th) t.join();
-  for (int g = 0; g < world; ++g)
-    if (st[g] != FMCW_OK) return fail(st[g], "device " + std::to_string(g) + ": " + msg[g]);
-  return FMCW_OK;
-}
-
 extern "C" {
 
 int fmcw_process(fmcw_ctx* c, const fmcw_params* p, const void* iq, int32_t in_dtype, int64_t F, float* prof,
@@ -2042,806 +1183,6 @@ int fmcw_synth_device(fmcw_ctx* c, const fmcw_params* p, int64_t frame0, int64_t
   a.cal = c->cal.as<float2>();
   HIPCHK(fmcw::launch_synth(a, pick(c, stream)));
   return FMCW_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// 2-D CA-CFAR over the RD map (kernels_cfar.hip)
-// ---------------------------------------------------------------------------
-static int cfar_check_impl(const fmcw_cfar_params* q, int32_t nr, int32_t nd, int32_t* n_train_full) {
-  if (!q) return fail(FMCW_E_ARG, "cfar params is NULL");
-  if (nr < 16 || nr > 2048 || (nr & (nr - 1))) return fail(FMCW_E_ARG, "cfar: nr must be a power of two in [16, 2048]");
-  if (nd < 4 || nd > 1024 || (nd & (nd - 1))) return fail(FMCW_E_ARG, "cfar: nd must be a power of two in [4, 1024]");
-  if (q->guard_r < 0 || q->guard_d < 0 || q->train_r < 0 || q->train_d < 0)
-    return fail(FMCW_E_ARG, "cfar: guard and training half-widths must be >= 0");
-  if (q->guard_r > 16 || q->guard_d > 16 || q->train_r > 16 || q->train_d > 16 || q->guard_r + q->train_r > 16 ||
-      q->guard_d + q->train_d > 16)
-    return fail(FMCW_E_ARG, "cfar: guard + train must be <= 16 in range (Wr) and in Doppler (Wd)");
-  if (q->train_r + q->train_d < 1) return fail(FMCW_E_ARG, "cfar: train_r + train_d must be >= 1");
-  const int Wr = q->guard_r + q->train_r, Wd = q->guard_d + q->train_d;
-  if (2 * Wd + 1 > nd) return fail(FMCW_E_ARG, "cfar: the Doppler window 2 Wd + 1 exceeds nd");
-  if (2 * Wr + 1 > nr) return fail(FMCW_E_ARG, "cfar: the range window 2 Wr + 1 exceeds nr");
-  if (!(q->alpha > 0.f) || !std::isfinite(q->alpha)) return fail(FMCW_E_ARG, "cfar: alpha must be finite and > 0");
-  if (q->r_lo > q->r_hi) return fail(FMCW_E_ARG, "cfar: r_lo > r_hi");
-  if (!(q->r_lo == 0 && q->r_hi == 0) && (q->r_lo < 1 || q->r_hi > nr))
-    return fail(FMCW_E_ARG, "cfar: the gate r_lo..r_hi must lie in 1..nr (or be 0, 0 for all rows)");
-  if (q->max_det < 1 || q->max_det > 1024) return fail(FMCW_E_ARG, "cfar: max_det must be in [1, 1024]");
-  if (q->flags & ~FMCW_CFAR_LOCAL_MAX) return fail(FMCW_E_ARG, "cfar: unknown flag bits");
-  if (n_train_full) *n_train_full = (2 * Wr + 1) * (2 * Wd + 1) - (2 * q->guard_r + 1) * (2 * q->guard_d + 1);
-  return FMCW_OK;
-}
-
-static int cfar_host_one(fmcw_ctx* c, const fmcw_cfar_params* q, const char* rd, int32_t dtype, int64_t F, int32_t nr,
-                         int32_t nd, int32_t* count, int32_t* ridx, int32_t* didx, float* power, float* noise,
-                         uint8_t* mask) {
-  CHK(set_device(c));
-  hipStream_t s = c->stream;
-  const int K = q->max_det;
-  const size_t fin = (size_t)nr * nd * esize(dtype), fmask = (size_t)nr * nd;
-  const int64_t Fc = host_chunk(fin, F);
-  Arena ar;
-  const size_t o_count = ar.add((size_t)F * 4), o_ridx = ar.add((size_t)F * K * 4), o_didx = ar.add((size_t)F * K * 4),
-               o_pow = ar.add((size_t)F * K * 4), o_noise = ar.add((size_t)F * K * 4);
-  CHK(c->cf_out.ensure(ar.off));
-  CHK(c->cf_in.ensure((size_t)Fc * fin));
-  if (mask) CHK(c->cf_mask.ensure((size_t)Fc * fmask));
-  char* const o = c->cf_out.as<char>();
-  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
-    const int64_t nf = std::min(Fc, F - f0);
-    HIPCHK(hipMemcpyAsync(c->cf_in.p, rd + (size_t)f0 * fin, (size_t)nf * fin, hipMemcpyHostToDevice, s));
-    CHK(fmcw_cfar_device(c, q, c->cf_in.p, dtype, nf, nr, nd, reinterpret_cast<int32_t*>(o + o_count) + f0,
-                         reinterpret_cast<int32_t*>(o + o_ridx) + f0 * K, reinterpret_cast<int32_t*>(o + o_didx) + f0 * K,
-                         reinterpret_cast<float*>(o + o_pow) + f0 * K, reinterpret_cast<float*>(o + o_noise) + f0 * K,
-                         mask ? c->cf_mask.as<uint8_t>() : nullptr, s));
-    if (mask) HIPCHK(hipMemcpyAsync(mask + (size_t)f0 * fmask, c->cf_mask.p, (size_t)nf * fmask, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));           // the chunk buffers are reused by the next chunk
-  }
-  HIPCHK(hipMemcpyAsync(count, o + o_count, (size_t)F * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(ridx, o + o_ridx, (size_t)F * K * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(didx, o + o_didx, (size_t)F * K * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(power, o + o_pow, (size_t)F * K * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(noise, o + o_noise, (size_t)F * K * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return FMCW_OK;
-}
-
-extern "C" {
-
-int fmcw_cfar_check(const fmcw_cfar_params* q, int32_t nr, int32_t nd, int32_t* n_train_full) {
-  return cfar_check_impl(q, nr, nd, n_train_full);
-}
-
-int fmcw_cfar_alpha(int32_t n_train, double pfa, float* alpha) {
-  if (!alpha) return fail(FMCW_E_ARG, "alpha is NULL");
-  if (n_train < 1) return fail(FMCW_E_ARG, "cfar: n_train must be >= 1");
-  if (!(pfa > 0.0 && pfa < 1.0)) return fail(FMCW_E_ARG, "cfar: pfa must be in (0, 1)");
-  *alpha = (float)((double)n_train * std::expm1(-std::log(pfa) / (double)n_train));   // N (pfa^(-1/N) - 1)
-  return FMCW_OK;
-}
-
-int fmcw_cfar_device(fmcw_ctx* c, const fmcw_cfar_params* q, const void* d_rd, int32_t rd_dtype, int64_t F, int32_t nr,
-                     int32_t nd, int32_t* d_count, int32_t* d_ridx, int32_t* d_didx, float* d_power, float* d_noise,
-                     uint8_t* d_mask, void* stream) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  CHK(cfar_check_impl(q, nr, nd, nullptr));
-  if (rd_dtype != FMCW_C64 && rd_dtype != FMCW_C32H) return fail(FMCW_E_ARG, "bad rd_dtype");
-  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
-  if (F == 0) return FMCW_OK;
-  if (!d_rd || !d_count || !d_ridx || !d_didx || !d_power || !d_noise) return fail(FMCW_E_ARG, "required pointer is NULL");
-  if (reinterpret_cast<uintptr_t>(d_rd) & 15) return fail(FMCW_E_ARG, "cfar: d_rd must be 16-byte aligned");
-  CHK(set_device(c));
-  hipStream_t s = pick(c, stream);
-  fmcw::CfarArgs a{};
-  a.h = rd_dtype == FMCW_C32H;
-  a.scale = a.h ? (float)nr * (float)nd : 1.f;
-  a.NR = nr; a.ND = nd;
-  a.gr = q->guard_r; a.gd = q->guard_d; a.tr = q->train_r; a.td = q->train_d;
-  a.g0 = q->r_lo == 0 ? 0 : q->r_lo - 1;
-  a.g1 = q->r_hi == 0 ? nr - 1 : q->r_hi - 1;
-  a.K = q->max_det;
-  a.local_max = (q->flags & FMCW_CFAR_LOCAL_MAX) ? 1 : 0;
-  a.alpha = q->alpha;
-  fmcw::cfar_plan(a, F);
-  // frames per launch pair: at most 256 MiB of list scratch (the lists hold max_det entries per wave;
-  // FMCW_CFAR_SCRATCH, in bytes, overrides, for tests of the launch seams)
-  const size_t per = fmcw::cfar_scratch_per_frame(a);
-  size_t budget = (size_t)256 << 20;
-  if (const char* e = std::getenv("FMCW_CFAR_SCRATCH"); e && std::atoll(e) > 0) budget = (size_t)std::atoll(e);
-  const int64_t Fc = std::max<int64_t>(1, std::min<int64_t>({F, (int64_t)(budget / per), (int64_t)32768}));
-  const size_t nsub = (size_t)a.strips * a.tiles * a.waves;
-  const size_t list_bytes = (size_t)Fc * nsub * a.K * sizeof(float4);
-  int st = FMCW_OK;
-  char* scr = static_cast<char*>(c->cfar_scr.get(s, list_bytes + (size_t)Fc * nsub * 4, &st));
-  CHK(st);
-  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
-  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
-    a.F = std::min(Fc, F - f0);
-    a.rd = static_cast<const char*>(d_rd) + (size_t)f0 * fin;
-    a.sub_list = reinterpret_cast<float4*>(scr);
-    a.sub_count = reinterpret_cast<int32_t*>(scr + list_bytes);
-    a.det_count = d_count + f0;
-    a.det_ridx = d_ridx + f0 * a.K;
-    a.det_didx = d_didx + f0 * a.K;
-    a.det_power = d_power + f0 * a.K;
-    a.det_noise = d_noise + f0 * a.K;
-    a.mask = d_mask ? d_mask + (size_t)f0 * nr * nd : nullptr;
-    StageTimer tm(c, 10, s);
-    HIPCHK(fmcw::launch_cfar(a, s));
-    tm.done();
-  }
-  CHK(c->cfar_scr.done(s));
-  return FMCW_OK;
-}
-
-int fmcw_cfar(fmcw_ctx* c, const fmcw_cfar_params* q, const void* rd, int32_t rd_dtype, int64_t F, int32_t nr, int32_t nd,
-              int32_t* count, int32_t* ridx, int32_t* didx, float* power, float* noise, uint8_t* mask) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  CHK(cfar_check_impl(q, nr, nd, nullptr));
-  if (rd_dtype != FMCW_C64 && rd_dtype != FMCW_C32H) return fail(FMCW_E_ARG, "bad rd_dtype");
-  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
-  if (F == 0) return FMCW_OK;
-  if (!rd || !count || !ridx || !didx || !power || !noise) return fail(FMCW_E_ARG, "required pointer is NULL");
-  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
-  const int K = q->max_det;
-  // frames are independent: contiguous shards, each written in place
-  return over_devices(c, F, [&](fmcw_ctx* d, int, int64_t f0, int64_t n) {
-    return cfar_host_one(d, q, static_cast<const char*>(rd) + (size_t)f0 * fin, rd_dtype, n, nr, nd, count + f0,
-                         ridx + f0 * K, didx + f0 * K, power + f0 * K, noise + f0 * K,
-                         mask ? mask + (size_t)f0 * nr * nd : nullptr);
-  });
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// Doppler-time and range-time signatures of the RD map (kernels_sig.hip)
-// ---------------------------------------------------------------------------
-static int sig_check_impl(const fmcw_sig_params* q, int32_t nr, int32_t nd) {
-  if (!q) return fail(FMCW_E_ARG, "sig params is NULL");
-  if (nr < 16 || nr > 2048 || (nr & (nr - 1))) return fail(FMCW_E_ARG, "sig: nr must be a power of two in [16, 2048]");
-  if (nd < 4 || nd > 1024 || (nd & (nd - 1))) return fail(FMCW_E_ARG, "sig: nd must be a power of two in [4, 1024]");
-  if (q->r_lo > q->r_hi) return fail(FMCW_E_ARG, "sig: r_lo > r_hi");
-  if (!(q->r_lo == 0 && q->r_hi == 0) && (q->r_lo < 1 || q->r_hi > nr))
-    return fail(FMCW_E_ARG, "sig: the gate r_lo..r_hi must lie in 1..nr (or be 0, 0 for all rows)");
-  if (q->track_half < 0 || q->track_half > 64) return fail(FMCW_E_ARG, "sig: track_half must be in [0, 64]");
-  if (q->dc_half < -1) return fail(FMCW_E_ARG, "sig: dc_half must be >= -1 (-1 leaves no Doppler bin out)");
-  if (2 * (int64_t)q->dc_half + 1 >= nd) return fail(FMCW_E_ARG, "sig: 2 dc_half + 1 must be < nd");
-  if (q->flags & ~FMCW_SIG_DB) return fail(FMCW_E_ARG, "sig: unknown flag bits");
-  if (!(q->floor_db < 0.f) || !std::isfinite(q->floor_db)) return fail(FMCW_E_ARG, "sig: floor_db must be finite and < 0");
-  return FMCW_OK;
-}
-
-// One shard of fmcw_sig: both maps and both maxima of frames [0, F) into the context's sg_out
-// ([F][nd], [F][nr], 2 floats), chunk by chunk.  The maps stay there for sig_host_finish.
-namespace {
-struct SigOut {
-  size_t o_dt, o_rt, o_max, bytes;
-  SigOut(int64_t F, int nr, int nd) {
-    Arena ar;
-    o_dt = ar.add((size_t)F * nd * 4);
-    o_rt = ar.add((size_t)F * nr * 4);
-    o_max = ar.add(8);
-    bytes = ar.off;
-  }
-};
-}  // namespace
-
-static int sig_host_one(fmcw_ctx* c, const fmcw_sig_params* q, const char* rd, int32_t dtype, int64_t F, int32_t nr,
-                        int32_t nd, const int32_t* center, int32_t cstride, float* mx) {
-  CHK(set_device(c));
-  hipStream_t s = c->stream;
-  const size_t fin = (size_t)nr * nd * esize(dtype);
-  const int64_t Fc = host_chunk(fin, F);
-  const SigOut so(F, nr, nd);
-  CHK(c->sg_out.ensure(so.bytes));
-  CHK(c->sg_in.ensure((size_t)Fc * fin));
-  char* const o = c->sg_out.as<char>();
-  HIPCHK(hipMemsetAsync(o + so.o_max, 0, 8, s));
-  if (center) {
-    CHK(c->sg_ctr.ensure((size_t)F * cstride * 4));
-    HIPCHK(hipMemcpyAsync(c->sg_ctr.p, center, (size_t)F * cstride * 4, hipMemcpyHostToDevice, s));
-  }
-  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
-    const int64_t nf = std::min(Fc, F - f0);
-    HIPCHK(hipMemcpyAsync(c->sg_in.p, rd + (size_t)f0 * fin, (size_t)nf * fin, hipMemcpyHostToDevice, s));
-    CHK(fmcw_sig_device(c, q, c->sg_in.p, dtype, nf, nr, nd, center ? c->sg_ctr.as<int32_t>() + f0 * cstride : nullptr,
-                        cstride, reinterpret_cast<float*>(o + so.o_dt) + f0 * nd,
-                        reinterpret_cast<float*>(o + so.o_rt) + f0 * nr, reinterpret_cast<float*>(o + so.o_max),
-                        reinterpret_cast<float*>(o + so.o_max) + 1, s));
-    HIPCHK(hipStreamSynchronize(s));           // the chunk buffer is reused by the next chunk
-  }
-  HIPCHK(hipMemcpyAsync(mx, o + so.o_max, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return FMCW_OK;
-}
-
-// The shard's maps to the host, in dB relative to the global maxima gmx when db.
-static int sig_host_finish(fmcw_ctx* c, int64_t F, int32_t nr, int32_t nd, bool db, const float* gmx, float floor_db,
-                           float* dt, float* rt) {
-  CHK(set_device(c));
-  hipStream_t s = c->stream;
-  const SigOut so(F, nr, nd);
-  char* const o = c->sg_out.as<char>();
-  float* const d_dt = reinterpret_cast<float*>(o + so.o_dt);
-  float* const d_rt = reinterpret_cast<float*>(o + so.o_rt);
-  float* const d_mx = reinterpret_cast<float*>(o + so.o_max);
-  if (db) {
-    HIPCHK(hipMemcpyAsync(d_mx, gmx, 8, hipMemcpyHostToDevice, s));
-    if (dt) CHK(fmcw_sig_db_device(c, d_dt, F * nd, d_mx, floor_db, d_dt, s));
-    if (rt) CHK(fmcw_sig_db_device(c, d_rt, F * nr, d_mx + 1, floor_db, d_rt, s));
-  }
-  if (dt) HIPCHK(hipMemcpyAsync(dt, d_dt, (size_t)F * nd * 4, hipMemcpyDeviceToHost, s));
-  if (rt) HIPCHK(hipMemcpyAsync(rt, d_rt, (size_t)F * nr * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return FMCW_OK;
-}
-
-extern "C" {
-
-int fmcw_sig_check(const fmcw_sig_params* q, int32_t nr, int32_t nd) { return sig_check_impl(q, nr, nd); }
-
-int fmcw_sig_device(fmcw_ctx* c, const fmcw_sig_params* q, const void* d_rd, int32_t rd_dtype, int64_t F, int32_t nr,
-                    int32_t nd, const int32_t* d_center, int32_t center_stride, float* d_doppler_time,
-                    float* d_range_time, float* d_dt_max, float* d_rt_max, void* stream) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  CHK(sig_check_impl(q, nr, nd));
-  if (rd_dtype != FMCW_C64 && rd_dtype != FMCW_C32H) return fail(FMCW_E_ARG, "bad rd_dtype");
-  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
-  if (!d_doppler_time && !d_range_time) return fail(FMCW_E_ARG, "sig: both maps are NULL");
-  if (d_center && center_stride < 1) return fail(FMCW_E_ARG, "sig: center_stride must be >= 1");
-  if (F == 0) return FMCW_OK;
-  if (!d_rd) return fail(FMCW_E_ARG, "required pointer is NULL");
-  if (reinterpret_cast<uintptr_t>(d_rd) & 15) return fail(FMCW_E_ARG, "sig: d_rd must be 16-byte aligned");
-  CHK(set_device(c));
-  hipStream_t s = pick(c, stream);
-  fmcw::SigArgs a{};
-  a.h = rd_dtype == FMCW_C32H;
-  a.scale2 = a.h ? ((float)nr * (float)nd) * ((float)nr * (float)nd) : 1.f;
-  a.NR = nr; a.ND = nd;
-  a.g0 = q->r_lo == 0 ? 0 : q->r_lo - 1;
-  a.g1 = q->r_hi == 0 ? nr - 1 : q->r_hi - 1;
-  a.th = q->track_half;
-  a.dc = q->dc_half;
-  a.center = d_center;
-  a.cstride = d_center ? center_stride : 0;
-  a.dt = d_doppler_time; a.rt = d_range_time;
-  a.dt_max = d_doppler_time ? d_dt_max : nullptr;
-  a.rt_max = d_range_time ? d_rt_max : nullptr;
-  fmcw::sig_plan(a);
-  // frames per launch: at most 256 MiB of column-sum scratch (the results do not depend on the cut)
-  const size_t per = fmcw::sig_scratch_per_frame(a);
-  const int64_t Fc = std::max<int64_t>(1, std::min<int64_t>({F, per ? (int64_t)(((size_t)256 << 20) / per) : F,
-                                                             (int64_t)0x7fffffff / 256}));
-  if (per) {
-    int st = FMCW_OK;
-    a.part = static_cast<float*>(c->sig_scr.get(s, (size_t)Fc * per, &st));
-    CHK(st);
-  }
-  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
-  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
-    a.F = std::min(Fc, F - f0);
-    a.rd = static_cast<const char*>(d_rd) + (size_t)f0 * fin;
-    a.center = d_center ? d_center + f0 * center_stride : nullptr;
-    a.dt = d_doppler_time ? d_doppler_time + f0 * nd : nullptr;
-    a.rt = d_range_time ? d_range_time + f0 * nr : nullptr;
-    HIPCHK(fmcw::launch_sig(a, s));
-  }
-  if (per) CHK(c->sig_scr.done(s));
-  return FMCW_OK;
-}
-
-int fmcw_sig_db_device(fmcw_ctx* c, const float* d_map, int64_t n, const float* d_max, float floor_db, float* d_out,
-                       void* stream) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  if (n < 0) return fail(FMCW_E_ARG, "n < 0");
-  if (!(floor_db < 0.f) || !std::isfinite(floor_db)) return fail(FMCW_E_ARG, "sig: floor_db must be finite and < 0");
-  if (n == 0) return FMCW_OK;
-  if (!d_map || !d_max || !d_out) return fail(FMCW_E_ARG, "required pointer is NULL");
-  CHK(set_device(c));
-  HIPCHK(fmcw::launch_sig_db(d_map, n, d_max, floor_db, d_out, pick(c, stream)));
-  return FMCW_OK;
-}
-
-int fmcw_sig(fmcw_ctx* c, const fmcw_sig_params* q, const void* rd, int32_t rd_dtype, int64_t F, int32_t nr, int32_t nd,
-             const int32_t* center, int32_t center_stride, float* doppler_time, float* range_time, float* dt_max,
-             float* rt_max) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  CHK(sig_check_impl(q, nr, nd));
-  if (rd_dtype != FMCW_C64 && rd_dtype != FMCW_C32H) return fail(FMCW_E_ARG, "bad rd_dtype");
-  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
-  if (!doppler_time && !range_time) return fail(FMCW_E_ARG, "sig: both maps are NULL");
-  if (center && center_stride < 1) return fail(FMCW_E_ARG, "sig: center_stride must be >= 1");
-  if (F == 0) {
-    if (dt_max) *dt_max = 0.f;
-    if (rt_max) *rt_max = 0.f;
-    return FMCW_OK;
-  }
-  if (!rd) return fail(FMCW_E_ARG, "required pointer is NULL");
-  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
-  const int world = 1 + (int)c->peers.size();
-  std::vector<float> mx(2 * (size_t)world, 0.f);
-  // frames are independent: contiguous shards; every shard forms both maps on its device
-  CHK(over_devices(c, F, [&](fmcw_ctx* d, int g, int64_t f0, int64_t n) {
-    return sig_host_one(d, q, static_cast<const char*>(rd) + (size_t)f0 * fin, rd_dtype, n, nr, nd,
-                        center ? center + f0 * center_stride : nullptr, center_stride, &mx[2 * (size_t)g]);
-  }));
-  float gmx[2] = {0.f, 0.f};                   // a maximum of non-negative floats does not depend on order
-  for (int g = 0; g < world; ++g) {
-    gmx[0] = std::max(gmx[0], mx[2 * (size_t)g]);
-    gmx[1] = std::max(gmx[1], mx[2 * (size_t)g + 1]);
-  }
-  if (dt_max) *dt_max = gmx[0];
-  if (rt_max) *rt_max = gmx[1];
-  // second pass, after the maxima are combined (:282-283): dB relative to the global maximum, then home
-  const bool db = (q->flags & FMCW_SIG_DB) != 0;
-  return over_devices(c, F, [&](fmcw_ctx* d, int, int64_t f0, int64_t n) {
-    return sig_host_finish(d, n, nr, nd, db, gmx, q->floor_db, doppler_time ? doppler_time + f0 * nd : nullptr,
-                           range_time ? range_time + f0 * nr : nullptr);
-  });
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// Targets from the CFAR detection lists (kernels_cluster.hip)
-// ---------------------------------------------------------------------------
-static int cluster_check_impl(const fmcw_cluster_params* q, int32_t nr, int32_t nd, int32_t max_det) {
-  if (!q) return fail(FMCW_E_ARG, "cluster params is NULL");
-  if (nr < 16 || nr > 2048 || (nr & (nr - 1))) return fail(FMCW_E_ARG, "cluster: nr must be a power of two in [16, 2048]");
-  if (nd < 4 || nd > 1024 || (nd & (nd - 1))) return fail(FMCW_E_ARG, "cluster: nd must be a power of two in [4, 1024]");
-  if (q->link_r < 0 || q->link_r > 8 || q->link_d < 0 || q->link_d > 8)
-    return fail(FMCW_E_ARG, "cluster: link_r and link_d must be in [0, 8]");
-  if (2 * q->link_d + 1 > nd) return fail(FMCW_E_ARG, "cluster: the Doppler link 2 link_d + 1 exceeds nd");
-  if (q->min_cells < 1 || q->min_cells > 1024) return fail(FMCW_E_ARG, "cluster: min_cells must be in [1, 1024]");
-  if (q->max_tgt < 1 || q->max_tgt > 64) return fail(FMCW_E_ARG, "cluster: max_tgt must be in [1, 64]");
-  if (max_det < 1 || max_det > 1024) return fail(FMCW_E_ARG, "cluster: max_det must be in [1, 1024]");
-  if (q->flags != 0) return fail(FMCW_E_ARG, "cluster: unknown flag bits");
-  return FMCW_OK;
-}
-
-namespace {
-// byte offsets of one shard's outputs in the context's cl_out: the fmcw_targets members in
-// declaration order, then det_label
-struct ClusterOut {
-  size_t o[12], bytes;
-  ClusterOut(int64_t F, int M, int K) {
-    Arena ar;
-    o[0] = ar.add((size_t)F * 4);
-    for (int i = 1; i < 11; ++i) o[i] = ar.add((size_t)F * M * 4);
-    o[11] = ar.add((size_t)F * K * 4);
-    bytes = ar.off;
-  }
-};
-}  // namespace
-
-static int cluster_host_one(fmcw_ctx* c, const fmcw_cluster_params* q, int64_t F, int32_t nr, int32_t nd, int32_t K,
-                            const int32_t* count, const int32_t* ridx, const int32_t* didx, const float* power,
-                            const float* noise, const fmcw_targets& out, int32_t* label) {
-  CHK(set_device(c));
-  hipStream_t s = c->stream;
-  const int M = q->max_tgt;
-  const size_t flist = (size_t)K * 4;
-  const int64_t Fc = host_chunk(4 + 4 * flist, F);
-  const ClusterOut co(F, M, K);
-  Arena in;
-  const size_t i_count = in.add((size_t)Fc * 4), i_ridx = in.add((size_t)Fc * flist), i_didx = in.add((size_t)Fc * flist),
-               i_pow = in.add((size_t)Fc * flist), i_noise = in.add((size_t)Fc * flist);
-  CHK(c->cl_out.ensure(co.bytes));
-  CHK(c->cl_in.ensure(in.off));
-  char* const o = c->cl_out.as<char>();
-  char* const di = c->cl_in.as<char>();
-  void* const host[12] = {out.tgt_count, out.cells, out.peak_range_idx, out.peak_doppler_idx, out.extent_r, out.extent_d,
-                          out.peak_power, out.peak_noise, out.power, out.range, out.doppler, label};
-  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
-    const int64_t nf = std::min(Fc, F - f0);
-    HIPCHK(hipMemcpyAsync(di + i_count, count + f0, (size_t)nf * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(di + i_ridx, ridx + f0 * K, (size_t)nf * flist, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(di + i_didx, didx + f0 * K, (size_t)nf * flist, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(di + i_pow, power + f0 * K, (size_t)nf * flist, hipMemcpyHostToDevice, s));
-    if (noise) HIPCHK(hipMemcpyAsync(di + i_noise, noise + f0 * K, (size_t)nf * flist, hipMemcpyHostToDevice, s));
-    fmcw_targets d{};
-    d.tgt_count = reinterpret_cast<int32_t*>(o + co.o[0]) + f0;
-    int32_t** const ip[5] = {&d.cells, &d.peak_range_idx, &d.peak_doppler_idx, &d.extent_r, &d.extent_d};
-    float** const fp[5] = {&d.peak_power, &d.peak_noise, &d.power, &d.range, &d.doppler};
-    for (int i = 0; i < 5; ++i) {
-      *ip[i] = host[1 + i] ? reinterpret_cast<int32_t*>(o + co.o[1 + i]) + f0 * M : nullptr;
-      *fp[i] = host[6 + i] ? reinterpret_cast<float*>(o + co.o[6 + i]) + f0 * M : nullptr;
-    }
-    CHK(fmcw_cluster_device(c, q, nf, nr, nd, K, reinterpret_cast<int32_t*>(di + i_count),
-                            reinterpret_cast<int32_t*>(di + i_ridx), reinterpret_cast<int32_t*>(di + i_didx),
-                            reinterpret_cast<float*>(di + i_pow), noise ? reinterpret_cast<float*>(di + i_noise) : nullptr,
-                            &d, label ? reinterpret_cast<int32_t*>(o + co.o[11]) + f0 * K : nullptr, s));
-    HIPCHK(hipStreamSynchronize(s));           // the chunk buffers are reused by the next chunk
-  }
-  for (int i = 0; i < 12; ++i) {
-    if (!host[i]) continue;
-    const size_t bytes = (size_t)F * 4 * (i == 0 ? 1 : i == 11 ? K : M);
-    HIPCHK(hipMemcpyAsync(host[i], o + co.o[i], bytes, hipMemcpyDeviceToHost, s));
-  }
-  HIPCHK(hipStreamSynchronize(s));
-  return FMCW_OK;
-}
-
-extern "C" {
-
-int fmcw_cluster_check(const fmcw_cluster_params* q, int32_t nr, int32_t nd, int32_t max_det) {
-  return cluster_check_impl(q, nr, nd, max_det);
-}
-
-int fmcw_cluster_device(fmcw_ctx* c, const fmcw_cluster_params* q, int64_t F, int32_t nr, int32_t nd, int32_t max_det,
-                        const int32_t* d_count, const int32_t* d_ridx, const int32_t* d_didx, const float* d_power,
-                        const float* d_noise, const fmcw_targets* d_out, int32_t* d_label, void* stream) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  CHK(cluster_check_impl(q, nr, nd, max_det));
-  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
-  if (F == 0) return FMCW_OK;
-  if (!d_count || !d_ridx || !d_didx || !d_power || !d_out || !d_out->tgt_count)
-    return fail(FMCW_E_ARG, "required pointer is NULL");
-  CHK(set_device(c));
-  hipStream_t s = pick(c, stream);
-  fmcw::ClusterArgs a{};
-  a.ND = nd;
-  a.K = max_det;
-  a.link_r = q->link_r; a.link_d = q->link_d; a.min_cells = q->min_cells; a.max_tgt = q->max_tgt;
-  const int64_t K = max_det, M = q->max_tgt;
-  // one workgroup per frame: at most 2^20 frames per launch (the results do not depend on the cut)
-  const int64_t Fc = (int64_t)1 << 20;
-  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
-    a.F = std::min(Fc, F - f0);
-    a.det_count = d_count + f0;
-    a.det_ridx = d_ridx + f0 * K;
-    a.det_didx = d_didx + f0 * K;
-    a.det_power = d_power + f0 * K;
-    a.det_noise = d_noise ? d_noise + f0 * K : nullptr;
-    a.tgt_count = d_out->tgt_count + f0;
-    a.cells = d_out->cells ? d_out->cells + f0 * M : nullptr;
-    a.pk_ridx = d_out->peak_range_idx ? d_out->peak_range_idx + f0 * M : nullptr;
-    a.pk_didx = d_out->peak_doppler_idx ? d_out->peak_doppler_idx + f0 * M : nullptr;
-    a.ext_r = d_out->extent_r ? d_out->extent_r + f0 * M : nullptr;
-    a.ext_d = d_out->extent_d ? d_out->extent_d + f0 * M : nullptr;
-    a.pk_power = d_out->peak_power ? d_out->peak_power + f0 * M : nullptr;
-    a.pk_noise = d_out->peak_noise ? d_out->peak_noise + f0 * M : nullptr;
-    a.power = d_out->power ? d_out->power + f0 * M : nullptr;
-    a.range = d_out->range ? d_out->range + f0 * M : nullptr;
-    a.doppler = d_out->doppler ? d_out->doppler + f0 * M : nullptr;
-    a.det_label = d_label ? d_label + f0 * K : nullptr;
-    StageTimer tm(c, 11, s);
-    HIPCHK(fmcw::launch_cluster(a, s));
-    tm.done();
-  }
-  return FMCW_OK;
-}
-
-int fmcw_cluster(fmcw_ctx* c, const fmcw_cluster_params* q, int64_t F, int32_t nr, int32_t nd, int32_t max_det,
-                 const int32_t* count, const int32_t* ridx, const int32_t* didx, const float* power, const float* noise,
-                 const fmcw_targets* out, int32_t* label) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  CHK(cluster_check_impl(q, nr, nd, max_det));
-  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
-  if (F == 0) return FMCW_OK;
-  if (!count || !ridx || !didx || !power || !out || !out->tgt_count) return fail(FMCW_E_ARG, "required pointer is NULL");
-  const int64_t K = max_det, M = q->max_tgt;
-  // frames are independent: contiguous shards, each written in place
-  return over_devices(c, F, [&](fmcw_ctx* d, int, int64_t f0, int64_t n) {
-    fmcw_targets t{};
-    t.tgt_count = out->tgt_count + f0;
-    t.cells = out->cells ? out->cells + f0 * M : nullptr;
-    t.peak_range_idx = out->peak_range_idx ? out->peak_range_idx + f0 * M : nullptr;
-    t.peak_doppler_idx = out->peak_doppler_idx ? out->peak_doppler_idx + f0 * M : nullptr;
-    t.extent_r = out->extent_r ? out->extent_r + f0 * M : nullptr;
-    t.extent_d = out->extent_d ? out->extent_d + f0 * M : nullptr;
-    t.peak_power = out->peak_power ? out->peak_power + f0 * M : nullptr;
-    t.peak_noise = out->peak_noise ? out->peak_noise + f0 * M : nullptr;
-    t.power = out->power ? out->power + f0 * M : nullptr;
-    t.range = out->range ? out->range + f0 * M : nullptr;
-    t.doppler = out->doppler ? out->doppler + f0 * M : nullptr;
-    return cluster_host_one(d, q, n, nr, nd, max_det, count + f0, ridx + f0 * K, didx + f0 * K, power + f0 * K,
-                            noise ? noise + f0 * K : nullptr, t, label ? label + f0 * K : nullptr);
-  });
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// Tracks from the per-frame targets (kernels_track.hip)
-// ---------------------------------------------------------------------------
-static int track_check_impl(const fmcw_track_params* q, int32_t nr, int32_t nd, int32_t max_tgt) {
-  if (!q) return fail(FMCW_E_ARG, "track params is NULL");
-  if (nr < 16 || nr > 2048 || (nr & (nr - 1))) return fail(FMCW_E_ARG, "track: nr must be a power of two in [16, 2048]");
-  if (nd < 4 || nd > 1024 || (nd & (nd - 1))) return fail(FMCW_E_ARG, "track: nd must be a power of two in [4, 1024]");
-  if (max_tgt < 1 || max_tgt > fmcw::kTrackMax) return fail(FMCW_E_ARG, "track: max_tgt must be in [1, 64]");
-  if (!(std::isfinite(q->gate_r) && q->gate_r > 0.f)) return fail(FMCW_E_ARG, "track: gate_r must be finite and > 0");
-  if (!(std::isfinite(q->gate_d) && q->gate_d > 0.f)) return fail(FMCW_E_ARG, "track: gate_d must be finite and > 0");
-  if (!(q->gate_d < (float)(nd / 2))) return fail(FMCW_E_ARG, "track: gate_d must be below nd/2");
-  if (!(q->alpha_r > 0.f && q->alpha_r <= 1.f)) return fail(FMCW_E_ARG, "track: alpha_r must be in (0, 1]");
-  if (!(q->alpha_d > 0.f && q->alpha_d <= 1.f)) return fail(FMCW_E_ARG, "track: alpha_d must be in (0, 1]");
-  if (!(q->beta_r >= 0.f && q->beta_r <= 1.f)) return fail(FMCW_E_ARG, "track: beta_r must be in [0, 1]");
-  if (q->confirm_hits < 1 || q->confirm_hits > 255) return fail(FMCW_E_ARG, "track: confirm_hits must be in [1, 255]");
-  if (q->max_coast < 0 || q->max_coast > 255) return fail(FMCW_E_ARG, "track: max_coast must be in [0, 255]");
-  if (q->max_trk < 1 || q->max_trk > fmcw::kTrackMax) return fail(FMCW_E_ARG, "track: max_trk must be in [1, 64]");
-  if (q->flags != 0) return fail(FMCW_E_ARG, "track: unknown flag bits");
-  return FMCW_OK;
-}
-
-// rows [f0, f0 + nf) of every one of S sequences, between a host array of F rows per sequence and a
-// dense device array of nf rows per sequence
-static int track_rows(void* dev, void* host, int64_t S, int64_t F, int64_t f0, int64_t nf, size_t rowbytes, bool to_device,
-                      hipStream_t s) {
-  char* const h = static_cast<char*>(host) + (size_t)f0 * rowbytes;
-  const hipMemcpyKind kind = to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
-  if (nf == F || S == 1) {
-    if (to_device) HIPCHK(hipMemcpyAsync(dev, h, (size_t)S * nf * rowbytes, kind, s));
-    else HIPCHK(hipMemcpyAsync(h, dev, (size_t)S * nf * rowbytes, kind, s));
-    return FMCW_OK;
-  }
-  const size_t hp = (size_t)F * rowbytes, dp = (size_t)nf * rowbytes;
-  if (to_device) HIPCHK(hipMemcpy2DAsync(dev, dp, h, hp, dp, (size_t)S, kind, s));
-  else HIPCHK(hipMemcpy2DAsync(h, hp, dev, dp, dp, (size_t)S, kind, s));
-  return FMCW_OK;
-}
-
-static int track_host_one(fmcw_ctx* c, const fmcw_track_params* q, int64_t S, int64_t F, int32_t nr, int32_t nd, int32_t M,
-                          const int32_t* count, const float* range, const float* doppler, const float* power, void* state,
-                          const fmcw_tracks& out, int32_t* tgt_track) {
-  CHK(set_device(c));
-  hipStream_t s = c->stream;
-  const int T = q->max_trk;
-  const size_t sbytes = (size_t)fmcw::track_state_words(T) * 4;
-  const size_t frow = (size_t)M * 4, trow = (size_t)T * 4;
-  // frames per chunk: a chunk holds that many frames of every sequence of the shard
-  const int64_t Fc = host_chunk((size_t)S * (4 + 3 * frow), F);
-  Arena in, ou;
-  const size_t i_count = in.add((size_t)S * Fc * 4), i_r = in.add((size_t)S * Fc * frow), i_d = in.add((size_t)S * Fc * frow),
-               i_p = in.add((size_t)S * Fc * frow);
-  size_t o_off[10];
-  o_off[0] = ou.add((size_t)S * Fc * 4);
-  for (int i = 1; i < 9; ++i) o_off[i] = ou.add((size_t)S * Fc * trow);
-  o_off[9] = ou.add((size_t)S * Fc * frow);
-  CHK(c->tk_in.ensure(in.off));
-  CHK(c->tk_out.ensure(ou.off));
-  CHK(c->tk_state.ensure((size_t)S * sbytes));
-  char* const di = c->tk_in.as<char>();
-  char* const o = c->tk_out.as<char>();
-  if (state) HIPCHK(hipMemcpyAsync(c->tk_state.p, state, (size_t)S * sbytes, hipMemcpyHostToDevice, s));
-  else HIPCHK(hipMemsetAsync(c->tk_state.p, 0, (size_t)S * sbytes, s));
-  void* const host[10] = {out.trk_count, out.trk_id, out.trk_status, out.trk_age, out.trk_misses,
-                          out.trk_range, out.trk_range_rate, out.trk_doppler, out.trk_power, tgt_track};
-  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
-    const int64_t nf = std::min(Fc, F - f0);
-    CHK(track_rows(di + i_count, const_cast<int32_t*>(count), S, F, f0, nf, 4, true, s));
-    CHK(track_rows(di + i_r, const_cast<float*>(range), S, F, f0, nf, frow, true, s));
-    CHK(track_rows(di + i_d, const_cast<float*>(doppler), S, F, f0, nf, frow, true, s));
-    CHK(track_rows(di + i_p, const_cast<float*>(power), S, F, f0, nf, frow, true, s));
-    fmcw_tracks d{};
-    d.trk_count = reinterpret_cast<int32_t*>(o + o_off[0]);
-    int32_t** const ip[4] = {&d.trk_id, &d.trk_status, &d.trk_age, &d.trk_misses};
-    float** const fp[4] = {&d.trk_range, &d.trk_range_rate, &d.trk_doppler, &d.trk_power};
-    for (int i = 0; i < 4; ++i) {
-      *ip[i] = host[1 + i] ? reinterpret_cast<int32_t*>(o + o_off[1 + i]) : nullptr;
-      *fp[i] = host[5 + i] ? reinterpret_cast<float*>(o + o_off[5 + i]) : nullptr;
-    }
-    CHK(fmcw_track_device(c, q, S, nf, nr, nd, M, reinterpret_cast<int32_t*>(di + i_count),
-                          reinterpret_cast<float*>(di + i_r), reinterpret_cast<float*>(di + i_d),
-                          reinterpret_cast<float*>(di + i_p), c->tk_state.p, &d,
-                          tgt_track ? reinterpret_cast<int32_t*>(o + o_off[9]) : nullptr, s));
-    for (int i = 0; i < 10; ++i)
-      if (host[i]) CHK(track_rows(o + o_off[i], host[i], S, F, f0, nf, i == 0 ? 4 : i == 9 ? frow : trow, false, s));
-    HIPCHK(hipStreamSynchronize(s));           // the chunk buffers are reused by the next chunk
-  }
-  if (state) HIPCHK(hipMemcpyAsync(state, c->tk_state.p, (size_t)S * sbytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return FMCW_OK;
-}
-
-extern "C" {
-
-int fmcw_track_check(const fmcw_track_params* q, int32_t nr, int32_t nd, int32_t max_tgt) {
-  return track_check_impl(q, nr, nd, max_tgt);
-}
-
-int32_t fmcw_track_state_bytes(int32_t max_trk) {
-  if (max_trk < 1 || max_trk > fmcw::kTrackMax) return fail(FMCW_E_ARG, "track: max_trk must be in [1, 64]");
-  return fmcw::track_state_words(max_trk) * 4;
-}
-
-int fmcw_track_device(fmcw_ctx* c, const fmcw_track_params* q, int64_t S, int64_t F, int32_t nr, int32_t nd, int32_t max_tgt,
-                      const int32_t* d_count, const float* d_range, const float* d_doppler, const float* d_power,
-                      void* d_state, const fmcw_tracks* d_out, int32_t* d_tgt_track, void* stream) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  CHK(track_check_impl(q, nr, nd, max_tgt));
-  if (F < 0 || S < 0) return fail(FMCW_E_ARG, "S < 0 or F < 0");
-  if (S > 0x7fffffffLL || F > ((int64_t)1 << 40) / std::max<int64_t>(S, 1))
-    return fail(FMCW_E_ARG, "track: S must be below 2^31 and S * F at most 2^40");
-  if (F == 0 || S == 0) return FMCW_OK;
-  if (!d_count || !d_range || !d_doppler || !d_power || !d_state || !d_out || !d_out->trk_count)
-    return fail(FMCW_E_ARG, "required pointer is NULL");
-  CHK(set_device(c));
-  hipStream_t s = pick(c, stream);
-  fmcw::TrackArgs a{};
-  a.S = S; a.F = F; a.NR = nr; a.ND = nd; a.M = max_tgt; a.T = q->max_trk;
-  a.wr = (float)(1.0 / ((double)q->gate_r * q->gate_r));
-  a.wd = (float)(1.0 / ((double)q->gate_d * q->gate_d));
-  a.alpha_r = q->alpha_r; a.alpha_d = q->alpha_d; a.beta_r = q->beta_r;
-  a.confirm_hits = q->confirm_hits; a.max_coast = q->max_coast;
-  a.tgt_count = d_count; a.range = d_range; a.doppler = d_doppler; a.power = d_power;
-  a.state = static_cast<uint32_t*>(d_state);
-  a.trk_count = d_out->trk_count;
-  a.trk_id = d_out->trk_id; a.trk_status = d_out->trk_status; a.trk_age = d_out->trk_age; a.trk_misses = d_out->trk_misses;
-  a.trk_range = d_out->trk_range; a.trk_rate = d_out->trk_range_rate; a.trk_doppler = d_out->trk_doppler;
-  a.trk_power = d_out->trk_power;
-  a.tgt_track = d_tgt_track;
-  StageTimer tm(c, 12, s);
-  HIPCHK(fmcw::launch_track(a, s));
-  tm.done();
-  return FMCW_OK;
-}
-
-int fmcw_track(fmcw_ctx* c, const fmcw_track_params* q, int64_t S, int64_t F, int32_t nr, int32_t nd, int32_t max_tgt,
-               const int32_t* count, const float* range, const float* doppler, const float* power, void* state,
-               const fmcw_tracks* out, int32_t* tgt_track) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  CHK(track_check_impl(q, nr, nd, max_tgt));
-  if (F < 0 || S < 0) return fail(FMCW_E_ARG, "S < 0 or F < 0");
-  if (S > 0x7fffffffLL || F > ((int64_t)1 << 40) / std::max<int64_t>(S, 1))
-    return fail(FMCW_E_ARG, "track: S must be below 2^31 and S * F at most 2^40");
-  if (F == 0 || S == 0) return FMCW_OK;
-  if (!count || !range || !doppler || !power || !out || !out->trk_count) return fail(FMCW_E_ARG, "required pointer is NULL");
-  const int64_t M = max_tgt, T = q->max_trk;
-  const size_t sbytes = (size_t)fmcw::track_state_words(q->max_trk) * 4;
-  // the frames of a sequence depend on each other, the sequences do not: contiguous shards of sequences
-  return over_devices(c, S, [&](fmcw_ctx* d, int, int64_t s0, int64_t n) {
-    const int64_t r0 = s0 * F;
-    fmcw_tracks t{};
-    t.trk_count = out->trk_count + r0;
-    t.trk_id = out->trk_id ? out->trk_id + r0 * T : nullptr;
-    t.trk_status = out->trk_status ? out->trk_status + r0 * T : nullptr;
-    t.trk_age = out->trk_age ? out->trk_age + r0 * T : nullptr;
-    t.trk_misses = out->trk_misses ? out->trk_misses + r0 * T : nullptr;
-    t.trk_range = out->trk_range ? out->trk_range + r0 * T : nullptr;
-    t.trk_range_rate = out->trk_range_rate ? out->trk_range_rate + r0 * T : nullptr;
-    t.trk_doppler = out->trk_doppler ? out->trk_doppler + r0 * T : nullptr;
-    t.trk_power = out->trk_power ? out->trk_power + r0 * T : nullptr;
-    return track_host_one(d, q, n, F, nr, nd, max_tgt, count + r0, range + r0 * M, doppler + r0 * M, power + r0 * M,
-                          state ? static_cast<char*>(state) + (size_t)s0 * sbytes : nullptr, t,
-                          tgt_track ? tgt_track + r0 * M : nullptr);
-  });
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// Frame-to-frame clutter filter of the RD map (kernels_mti.hip)
-// ---------------------------------------------------------------------------
-static int mti_check_impl(const fmcw_mti_params* q, int32_t nr, int32_t nd) {
-  if (!q) return fail(FMCW_E_ARG, "mti params is NULL");
-  if (nr < 16 || nr > 2048 || (nr & (nr - 1))) return fail(FMCW_E_ARG, "mti: nr must be a power of two in [16, 2048]");
-  if (nd < 4 || nd > 1024 || (nd & (nd - 1))) return fail(FMCW_E_ARG, "mti: nd must be a power of two in [4, 1024]");
-  if (!(std::isfinite(q->lambda) && q->lambda > 0.f && q->lambda <= 1.f))
-    return fail(FMCW_E_ARG, "mti: lambda must be finite and in (0, 1]");
-  if (q->flags & ~(FMCW_MTI_RAMP | FMCW_MTI_FREEZE)) return fail(FMCW_E_ARG, "mti: unknown flag bits");
-  return FMCW_OK;
-}
-
-// frames per lane in flight: the shipped depth of the dtype (FMCW_MTI_RING, one of 4 8 16,
-// overrides, for the measurement of tools/bench_mti.py)
-static int mti_ring(int32_t dtype) {
-  if (const char* e = std::getenv("FMCW_MTI_RING"); e && fmcw::mti_ring_ok(std::atoi(e))) return std::atoi(e);
-  return dtype == FMCW_C32H ? fmcw::kMtiRingC32H : fmcw::kMtiRingC64;
-}
-
-static int mti_sizes(int64_t S, int64_t F) {
-  if (F < 0 || S < 0) return fail(FMCW_E_ARG, "S < 0 or F < 0");
-  if (S > 0x7fffffffLL || F > ((int64_t)1 << 40) / std::max<int64_t>(S, 1))
-    return fail(FMCW_E_ARG, "mti: S must be below 2^31 and S * F at most 2^40");
-  return FMCW_OK;
-}
-
-// frames [f0, f0 + nf) of every one of S sequences, between a host array of F frames per sequence
-// and a dense device array of nf frames per sequence
-static int mti_frames(char* dev, char* host, int64_t S, int64_t F, int64_t f0, int64_t nf, size_t fbytes, bool to_device,
-                      hipStream_t s) {
-  const int64_t runs = nf == F ? 1 : S, per = nf == F ? S * nf : nf;
-  for (int64_t q = 0; q < runs; ++q) {
-    char* const h = host + ((size_t)q * F + f0) * fbytes;
-    char* const d = dev + (size_t)q * nf * fbytes;
-    if (to_device) HIPCHK(hipMemcpyAsync(d, h, (size_t)per * fbytes, hipMemcpyHostToDevice, s));
-    else HIPCHK(hipMemcpyAsync(h, d, (size_t)per * fbytes, hipMemcpyDeviceToHost, s));
-  }
-  return FMCW_OK;
-}
-
-static int mti_host_one(fmcw_ctx* c, const fmcw_mti_params* q, const char* rd, int32_t dtype, int64_t S, int64_t F, int32_t nr,
-                        int32_t nd, float* bg, int32_t* seen, char* out) {
-  CHK(set_device(c));
-  hipStream_t s = c->stream;
-  const size_t fin = (size_t)nr * nd * esize(dtype), bbytes = (size_t)nr * nd * 8;
-  // frames per chunk: a chunk holds that many frames of every sequence of the shard
-  const int64_t Fc = host_chunk((size_t)S * fin, F);
-  CHK(c->mt_rd.ensure((size_t)S * Fc * fin));
-  CHK(c->mt_bg.ensure((size_t)S * bbytes));
-  CHK(c->mt_seen.ensure((size_t)S * 4));
-  if (bg) {
-    HIPCHK(hipMemcpyAsync(c->mt_bg.p, bg, (size_t)S * bbytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->mt_seen.p, seen, (size_t)S * 4, hipMemcpyHostToDevice, s));
-  } else {
-    HIPCHK(hipMemsetAsync(c->mt_bg.p, 0, (size_t)S * bbytes, s));
-    HIPCHK(hipMemsetAsync(c->mt_seen.p, 0, (size_t)S * 4, s));
-  }
-  char* const d = c->mt_rd.as<char>();
-  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
-    const int64_t nf = std::min(Fc, F - f0);
-    CHK(mti_frames(d, const_cast<char*>(rd), S, F, f0, nf, fin, true, s));
-    CHK(fmcw_mti_device(c, q, d, dtype, S, nf, nr, nd, c->mt_bg.as<float>(), c->mt_seen.as<int32_t>(), out ? d : nullptr, s));
-    if (out) CHK(mti_frames(d, out, S, F, f0, nf, fin, false, s));
-    HIPCHK(hipStreamSynchronize(s));           // the chunk buffer is reused by the next chunk
-  }
-  if (bg) {
-    HIPCHK(hipMemcpyAsync(bg, c->mt_bg.p, (size_t)S * bbytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(seen, c->mt_seen.p, (size_t)S * 4, hipMemcpyDeviceToHost, s));
-  }
-  HIPCHK(hipStreamSynchronize(s));
-  return FMCW_OK;
-}
-
-extern "C" {
-
-int fmcw_mti_check(const fmcw_mti_params* q, int32_t nr, int32_t nd) { return mti_check_impl(q, nr, nd); }
-
-int32_t fmcw_mti_ring(int32_t rd_dtype) {
-  if (rd_dtype != FMCW_C64 && rd_dtype != FMCW_C32H) return fail(FMCW_E_ARG, "bad rd_dtype");
-  return mti_ring(rd_dtype);
-}
-
-int fmcw_mti_device(fmcw_ctx* c, const fmcw_mti_params* q, const void* d_rd, int32_t rd_dtype, int64_t S, int64_t F,
-                    int32_t nr, int32_t nd, float* d_bg, int32_t* d_seen, void* d_out, void* stream) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  CHK(mti_check_impl(q, nr, nd));
-  if (rd_dtype != FMCW_C64 && rd_dtype != FMCW_C32H) return fail(FMCW_E_ARG, "bad rd_dtype");
-  CHK(mti_sizes(S, F));
-  if ((q->flags & FMCW_MTI_FREEZE) && !d_out) return fail(FMCW_E_ARG, "mti: FREEZE without an output leaves nothing to do");
-  if (F == 0 || S == 0) return FMCW_OK;
-  if (!d_rd || !d_bg || !d_seen) return fail(FMCW_E_ARG, "required pointer is NULL");
-  const uintptr_t pr = reinterpret_cast<uintptr_t>(d_rd), po = reinterpret_cast<uintptr_t>(d_out);
-  if ((pr | po | reinterpret_cast<uintptr_t>(d_bg) | reinterpret_cast<uintptr_t>(d_seen)) & 15)
-    return fail(FMCW_E_ARG, "mti: d_rd, d_out, d_bg and d_seen must be 16-byte aligned");
-  const size_t fin = (size_t)nr * nd * esize(rd_dtype), total = (size_t)S * F * fin;
-  if (d_out && po != pr && po < pr + total && pr < po + total)
-    return fail(FMCW_E_ARG, "mti: d_out must be d_rd itself or not overlap it");
-  CHK(set_device(c));
-  hipStream_t s = pick(c, stream);
-  fmcw::MtiArgs a{};
-  a.rd = d_rd; a.out = d_out; a.bg = d_bg; a.seen = d_seen;
-  a.S = S; a.F = F;
-  a.n16 = (int64_t)(fin / 16);
-  a.h = rd_dtype == FMCW_C32H;
-  a.ring = mti_ring(rd_dtype);
-  a.lambda = q->lambda;
-  a.ramp = (q->flags & FMCW_MTI_RAMP) ? 1 : 0;
-  a.freeze = (q->flags & FMCW_MTI_FREEZE) ? 1 : 0;
-  StageTimer tm(c, 13, s);
-  HIPCHK(fmcw::launch_mti(a, s));
-  tm.done();
-  return FMCW_OK;
-}
-
-int fmcw_mti(fmcw_ctx* c, const fmcw_mti_params* q, const void* rd, int32_t rd_dtype, int64_t S, int64_t F, int32_t nr,
-             int32_t nd, float* bg, int32_t* seen, void* out) {
-  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  CHK(mti_check_impl(q, nr, nd));
-  if (rd_dtype != FMCW_C64 && rd_dtype != FMCW_C32H) return fail(FMCW_E_ARG, "bad rd_dtype");
-  CHK(mti_sizes(S, F));
-  if ((q->flags & FMCW_MTI_FREEZE) && !out) return fail(FMCW_E_ARG, "mti: FREEZE without an output leaves nothing to do");
-  if ((bg == nullptr) != (seen == nullptr)) return fail(FMCW_E_ARG, "mti: bg and seen must both be given or both be NULL");
-  if (F == 0 || S == 0) return FMCW_OK;
-  if (!rd) return fail(FMCW_E_ARG, "required pointer is NULL");
-  const size_t fin = (size_t)nr * nd * esize(rd_dtype), cells2 = (size_t)nr * nd * 2;
-  // the frames of a sequence depend on each other, the sequences do not: contiguous shards of sequences
-  return over_devices(c, S, [&](fmcw_ctx* d, int, int64_t s0, int64_t n) {
-    return mti_host_one(d, q, static_cast<const char*>(rd) + (size_t)s0 * F * fin, rd_dtype, n, F, nr, nd,
-                        bg ? bg + (size_t)s0 * cells2 : nullptr, seen ? seen + s0 : nullptr,
-                        out ? static_cast<char*>(out) + (size_t)s0 * F * fin : nullptr);
-  });
 }
 
 }  // extern "C"

@@ -39,6 +39,15 @@ def _host_iq(iq: np.ndarray):
     raise TypeError("iq must be complex64 [F][C][S] or float16 [F][C][S][2]")
 
 
+def _host_rd(rd: np.ndarray, lead: str):
+    """complex64 [lead][nr][nd]  or  float16 [lead][nr][nd][2] -> (contiguous array, dtype code)."""
+    if rd.dtype == np.complex64 and rd.ndim == 3:
+        return np.ascontiguousarray(rd), FMCW_C64
+    if rd.dtype == np.float16 and rd.ndim == 4 and rd.shape[-1] == 2:
+        return np.ascontiguousarray(rd), FMCW_C32H
+    raise TypeError(f"rd must be complex64 [{lead}][nr][nd] or float16 [{lead}][nr][nd][2]")
+
+
 class Engine:
     """fmcw_ctx on HIP device ``device`` -- an int, or a list of device ids for
     one context over several GPUs (the host-array calls then shard their work
@@ -249,12 +258,7 @@ class Engine:
         det_doppler_idx, det_power, det_noise [F][max_det] (1-based indices, 0 where unused) and,
         once set_taps has given the geometry's scales, range_m / speed_mps of every listed
         detection (NaN where unused); `mask` [F][nr][nd] uint8 when asked for."""
-        if rd.dtype == np.complex64 and rd.ndim == 3:
-            rd, dt = np.ascontiguousarray(rd), FMCW_C64
-        elif rd.dtype == np.float16 and rd.ndim == 4 and rd.shape[-1] == 2:
-            rd, dt = np.ascontiguousarray(rd), FMCW_C32H
-        else:
-            raise TypeError("rd must be complex64 [F][nr][nd] or float16 [F][nr][nd][2]")
+        rd, dt = _host_rd(rd, "F")
         F, nr, nd = rd.shape[:3]
         K = int(q.max_det)
         out = dict(det_count=np.zeros(F, np.int32), det_range_idx=np.zeros((F, max(K, 0)), np.int32),
@@ -305,12 +309,7 @@ class Engine:
         Returns doppler_time [F][nd], range_time [F][nr] (in dB with q.db), the global maxima dt_max,
         rt_max of the linear maps and, once set_taps has given the geometry, the axes speed_mps [nd]
         and range_m [nr]."""
-        if rd.dtype == np.complex64 and rd.ndim == 3:
-            rd, dt = np.ascontiguousarray(rd), FMCW_C64
-        elif rd.dtype == np.float16 and rd.ndim == 4 and rd.shape[-1] == 2:
-            rd, dt = np.ascontiguousarray(rd), FMCW_C32H
-        else:
-            raise TypeError("rd must be complex64 [F][nr][nd] or float16 [F][nr][nd][2]")
+        rd, dt = _host_rd(rd, "F")
         F, nr, nd = rd.shape[:3]
         stride = 0
         if center is not None:
@@ -542,12 +541,7 @@ class Engine:
         call returned, to carry the sequences on (both or neither; the caller's arrays are not written
         through).  Returns `out` (the shape and dtype of rd; None without want_out, which only learns
         the background), `bg` and `seen` after the last frame."""
-        if rd.dtype == np.complex64 and rd.ndim == 3:
-            rd, dt = np.ascontiguousarray(rd), FMCW_C64
-        elif rd.dtype == np.float16 and rd.ndim == 4 and rd.shape[-1] == 2:
-            rd, dt = np.ascontiguousarray(rd), FMCW_C32H
-        else:
-            raise TypeError("rd must be complex64 [S*F][nr][nd] or float16 [S*F][nr][nd][2]")
+        rd, dt = _host_rd(rd, "S*F")
         rows, nr, nd = rd.shape[:3]
         S = int(n_seq)
         if S < 1 or rows % S:

@@ -61,7 +61,7 @@ class Op:
 
     def launches(self, cfg):
         """k_rdx launches of the call on the single-pass schedule: one per chunk of the device call;
-        the host call makes one device call per 64 MiB of input (fmcw_api.cpp host_chunk)."""
+        the host call makes one device call per 64 MiB of input (api_internal.h host_chunk)."""
         if self.pipe == FMCW_PIPE_STREAMS:
             return 0
         per = lambda n: 1 if self.chunk <= 0 else -(-n // self.chunk)

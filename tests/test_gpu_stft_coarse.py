@@ -1,4 +1,4 @@
-"""GPU: fmcw_stft's coarse-to-fine max(P) (fmcw_api.cpp stft_coarse_max), used for the reference
+"""GPU: fmcw_stft's coarse-to-fine max(P) (api_stft.cpp stft_coarse_max), used for the reference
 nfft rule at large L (:273 nfft = 2^nextpow2(L) >= 2^18) with the 1024 log bins of :286-299.
 
 max(P) (:282-283) must be the maximum over every bin of every segment; the coarse pass bounds each
