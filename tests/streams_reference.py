@@ -1,0 +1,344 @@
+"""Storage-emulating float64 reference of the streams schedule (K1 k_range, K2 k_doppler, K3 k_detect
+of csrc/kernels_frame.hip), built on the oracle's own functions; test-side numpy code, no GPU.
+
+The streams schedule keeps two intermediates in memory, the range cube and the RD map, each as c64 or
+as c32h (include/fmcw.h, FMCW_C32H: fp16 pairs holding X / Nr and D / (Nr Nd)).  Everything behind a
+store reads what was stored:
+
+  K1   X = fft(...)                        cube  <- X, or fp16(X / Nr)
+       profile of fmcw_range_fft_device    from X itself (the registers, before the store)
+  K2   profile, mean, Doppler FFT          from the stored cube;   rd <- D, or fp16(D / (Nr Nd))
+  K3   peaks from K2's profile; the Doppler index from the stored rd; the slow-time row and the probe
+       column from the stored cube
+
+chains() runs that for the four (cube, rd) storage pairs at once, next to the plain chain
+(oracle.process_frames on the same input).  The input is the IQ as the device holds it, so a c32h input
+is rounded by the caller (iq_as_stored) and costs the reference nothing.  e_ref[key][frame] is the
+relative L2 distance of the emulated from the plain chain: what the fp16 stores upstream of that output
+cost in exact arithmetic, 0 where there is none.  The GPU tests hold the kernels to
+bound(e_ref) = 2 e_ref + TOL_FP32_REL_L2, never above TOL_FP16_REL_L2: the kernel rounds float32 values
+and the emulation float64 values, so the two may land on different fp16 neighbours (a second rounding
+error of the same size), and the float32 arithmetic adds its own bar.
+
+The RD map's error is normalised as everywhere in this suite (helpers.rd_rel_err: by ||rd||, but never
+by less than a tenth of the energy entering the Doppler FFT), for e_ref and for the kernels alike: every
+synthetic frame at Nd 2 and some at every size hold a static target, whose rows cancel in the mean
+removal to the rounding residue of the uncancelled data.
+"""
+from __future__ import annotations
+
+import dataclasses
+
+import numpy as np
+
+from fmcw_radar_processing_amd import params as P
+from oracle import oracle as O
+from tests import detect_reference as DR
+from tests.helpers import TOL_FP16_REL_L2, TOL_FP32_REL_L2, case, near_tie_frames, rd_rel_err, rel_l2
+
+C64, C32H = 0, 1                       # FMCW_C64, FMCW_C32H
+STORAGE = [(C64, C64), (C64, C32H), (C32H, C64), (C32H, C32H)]     # (cube, rd), and K1's (in, cube)
+E_REF_MAX = TOL_FP16_REL_L2 / 4        # the condition on the inputs (test_streams_reference_host)
+ROW_GAP = 1e-3                         # Doppler rows whose two largest magnitudes are closer are left out
+NOISE_SIGMA = 0.05
+KEYS = ("cube", "rd", "profile", "slow_mag", "tgt_range_mag", "probe")
+
+
+# --------------------------------------------------------------------------
+# geometries.  Nr 16 and 32 have no bin the default gate and threshold admit a synthetic tone in
+# (the profile peak of a tone of amplitude A is about 22 A nr, below range_thr 200 there), so those
+# cases open the gate and lower the threshold, as detect_reference.with_params does.
+# --------------------------------------------------------------------------
+SMALL = dict(range_thr=12.0, min_d=0.0, max_d=1.0e6, doppler_thr=2.0)
+
+# section 2 of the grid: (nts, pn, nr, nd, F) -> what it exercises
+SIZE_CASES = [
+    (16, 6, 16, 2, 6),          # both minima: T = 1 teams, 256 teams per K1 workgroup, one K2 tile of 256 rows for 16; pn > nd
+    (16, 40, 16, 1024, 4),      # K2 T = 64, 4-row tiles; pn < nd zero pad
+    (30, 7, 32, 4, 9),          # final radix-2 pass; S < NR; odd pn; invalid tail teams
+    (27, 5, 32, 8, 7),          # odd S; ND 8 in the no-LDS plan
+    (64, 16, 64, 8, 6),         # final radix-4 pass
+    (100, 70, 64, 64, 5),       # S > NR (truncate, the mean keeps all samples); C > ND
+    (200, 24, 128, 128, 5),     # final radix-8 pass; S > NR; ND 128 with T = 8
+    (256, 12, 256, 2, 5),       # ND 2 with full 256-row tiles
+    (512, 20, 512, 512, 4),     # ND 512: T = 32, pad 1 in 32, three passes; C < ND
+    (2048, 8, 2048, 2, 3),      # S = NR at 2048: the nt load path, teams of two waves, BlockSync
+    (2100, 12, 2048, 1024, 3),  # S > NR through team_sum<128>; ND 1024
+    (1024, 256, 1024, 256, 2),  # the single-pass geometry through the streams kernels
+    (64, 16, 256, 16, 5),       # ND 16 (one radix-16 pass, the first LDS plan): the deployed module's geometry
+    (100, 20, 128, 32, 5),      # ND 32: final radix-2 pass in K2
+]
+# section 3: the storage grid
+STORAGE_CASES = [(64, 16, 64, 8, 6), (200, 24, 128, 128, 5), (512, 20, 512, 512, 4), (1024, 256, 1024, 256, 2),
+                 (2100, 12, 2048, 1024, 3)]
+# section 4: FMCW_PAIR=1 against the default path, one geometry per ND of {2, 8, 16, 128, 1024}
+PAIR_CASES = [(16, 6, 16, 2, 6), (27, 5, 32, 8, 7), (64, 16, 256, 16, 5), (200, 24, 128, 128, 5), (16, 40, 16, 1024, 4)]
+
+# section 5: fmcw_range_fft_device (K1 with the profile); nd plays no part
+K1_CASES = [(16, 512, 16, 16, 3), (16, 40, 16, 16, 7), (100, 96, 64, 16, 7), (200, 48, 256, 16, 5),
+            (2048, 8, 2048, 16, 3), (2100, 12, 2048, 16, 3)]
+K1_CPT = (None, "1", "64")             # FMCW_K1_CPT: unset, 1, 64
+
+
+def k1_profile_paths(g, cpt_env) -> set:
+    """Which of k_range's profile paths a fmcw_range_fft_device call of geometry g takes, restated from
+    fmcw_range_fft_device (the choice of cpt and parts) and k_range (the flush per frame group of a
+    workgroup): 'store' (the workgroup holds the whole frame), 'parts' (an equal part of it: prof_part
+    and k_profile_reduce), 'atomic' (anything else), and 'tail' when the last workgroup has teams beyond
+    the last chirp."""
+    nts, pn, nr, nd, F = g
+    cpt = 8 if cpt_env is None else max(1, min(64, int(cpt_env)))
+    while cpt > 1 and pn % cpt:
+        cpt >>= 1
+    T = nr // 16
+    teams = 1 if T >= 256 else 256 // T
+    per_wg = teams * cpt
+    parts = pn // per_wg if (per_wg < pn and pn % per_wg == 0) else 0
+    nchirps = F * pn
+    paths = set()
+    for b in range(-(-nchirps // per_wg)):
+        groups = {}
+        for i in range(teams):
+            gi = b * per_wg + i * cpt
+            if gi < nchirps:
+                groups[gi // pn] = groups.get(gi // pn, 0) + 1
+            else:
+                paths.add("tail")
+        for nteam in groups.values():
+            span = nteam * cpt
+            paths.add("store" if span == pn else "parts" if parts > 1 and span * parts == pn else "atomic")
+    return paths
+
+
+ALL_NR = (16, 32, 64, 128, 256, 512, 1024, 2048)
+ALL_ND = (2, 4, 8, 16, 32, 64, 128, 256, 512, 1024)
+NEW_NR = (16, 32, 64)                  # sizes no test ran before this module
+NEW_ND = (2, 8, 128, 512, 1024)
+
+
+def case_id(g):
+    return f"{g[0]}x{g[1]}_nr{g[2]}_nd{g[3]}"
+
+
+def overrides(g) -> dict:
+    return dict(SMALL) if g[2] <= 32 else {}
+
+
+def build_case(g, mode=P.THROUGHPUT):
+    """(cfg, p, wr, wd, cal) of geometry g with its overrides; p carries the detection parameters as the
+    float32 values the C-ABI hands the kernels (detect_reference.oracle_params)."""
+    cfg, p, wr, wd, cal = case(g[0], g[1], g[2], g[3], mode)
+    cfg = dataclasses.replace(cfg, **overrides(g))
+    return cfg, DR.oracle_params(p, cfg, cfg.max_targets), wr, wd, cal
+
+
+def frame_ids(g, p) -> list:
+    """The synthetic frames of a case: the first F - 1 of frames 0, 1, .. that carry a tone and the
+    first that carries none, in ascending order (every case needs a frame with and one without a
+    target whatever F is; the generator leaves one frame in ten empty)."""
+    nts, pn, nr, nd, F = g
+    tone, empty, f = [], None, 0
+    while len(tone) < F - 1 or empty is None:
+        A = O.synth_frame_params(f, nr, nd, p["dist_per_bin"])["A"]
+        if A == 0 and empty is None:
+            empty = f
+        elif A > 0 and len(tone) < F - 1:
+            tone.append(f)
+        f += 1
+    return sorted(tone + [empty])
+
+
+def synth(g, p) -> np.ndarray:
+    nts, pn, nr, nd, F = g
+    return np.concatenate([O.synth_frames(1, pn, nts, nr, nd, p["dist_per_bin"], frame0=f) for f in frame_ids(g, p)])
+
+
+def storage_frames(g, cfg) -> np.ndarray:
+    """The frames of the storage grid, complex64 [F][C][S] (detect_reference.build_frame: calibration
+    tone, noise of sigma 1e-3, one tone each).  F - 1 frames carry a moving tone on a gate bin; frame
+    F // 2 carries one beyond the gate and so has no target.  No frame is empty or static: the RD map of
+    such a frame is noise or rounding residue only, which D / (Nr Nd) puts among the fp16 subnormals
+    where pn is far below nd (e_ref 5e-3 at 2100 x 12 -> 2048 x 1024), and the bars of the grid are
+    conditioned on e_ref <= E_REF_MAX."""
+    nts, pn, nr, nd, F = g
+    gate = DR.gate_bins(cfg)
+    g0, g1 = int(gate[0]), int(gate[-1])
+    rng = np.random.default_rng([nts, pn, nr, nd, 3])
+    frames = []
+    for f in range(F):
+        d = int(rng.integers(nd // 4, nd // 2)) * (1 if f % 2 else -1)     # fast: the mean removal leaves it whole
+        r = g1 + max(4, (nr // 2 - g1) // 2) if f == F // 2 else int(rng.integers(g0 + 2, g1 - 1))
+        t = DR.tone(0.1 + 0.1 * rng.random(), r, d, rng.random())
+        frames.append(DR.build_frame([t], True, nts, pn, nr, nd, 17, f))
+    return np.stack(frames)
+
+
+def noise_frame(g) -> np.ndarray:
+    """One white frame, complex64 [1][C][S]: the calibration tone plus CN(0, 0.05^2), no target.  Every
+    bin of the cube and of the RD map holds energy, which a tone-dominated frame's L2 does not test."""
+    nts, pn, nr, nd, _ = g
+    rng = np.random.default_rng([nts, pn, nr, nd, 7])
+    z = (NOISE_SIGMA / np.sqrt(2.0)) * (rng.standard_normal((pn, nts)) + 1j * rng.standard_normal((pn, nts)))
+    return (O.synth_cal(nts)[None, :] + z).astype(np.complex64)[None]
+
+
+def iq_as_stored(iq: np.ndarray, in_dtype: int):
+    """(what the device is given, the complex64 values it holds): iq itself for C64, the float16 pairs
+    [F][C][S][2] and their values for C32H."""
+    if in_dtype == C64:
+        return iq, iq
+    h = np.stack([iq.real, iq.imag], -1).astype(np.float16)
+    return h, h.astype(np.float32).view(np.complex64)[..., 0]
+
+
+# --------------------------------------------------------------------------
+# the emulated chain
+# --------------------------------------------------------------------------
+def fp16_round(z: np.ndarray, scale: float) -> np.ndarray:
+    """What a c32h store of z * scale holds, multiplied back: scale is a power of two, so only the
+    fp16 rounding of re and im (round to nearest even, numpy's astype) remains."""
+    with np.errstate(over="ignore"):
+        re = (z.real * scale).astype(np.float16).astype(np.float64)
+        im = (z.imag * scale).astype(np.float16).astype(np.float64)
+    return (re + 1j * im) / scale
+
+
+def emulate(iq, cal, p, wr, wd, cube_dtype=C64, rd_dtype=C64, probe_column=0) -> dict:
+    """oracle.process_frames(rd_all_rows) restated with the two stores between the stages.  Also
+    profile_k1, the profile fmcw_range_fft_device returns (from X before the store), and cube_peak, the
+    largest |re|, |im| of X / Nr (the fp16 range is 65504)."""
+    F, C, S = iq.shape
+    nr, nd, M = p["nr"], p["nd"], p["max_targets"]
+    out = dict(profile=np.zeros((F, nr)), profile_k1=np.zeros((F, nr)), tgt_range_idx=np.zeros((F, M), np.int32),
+               tgt_range_mag=np.zeros((F, M)), tgt_doppler_idx=np.zeros((F, M), np.int32),
+               tgt_count=np.zeros(F, np.int32), slow_mag=np.zeros((F, C)), cube=np.zeros((F, C, nr), np.complex128),
+               rd=np.zeros((F, nr, nd), np.complex128), probe=np.zeros(nr), cube_peak=0.0)
+    for f in range(F):
+        x = iq[f].astype(np.complex128).T
+        X = O.fast_time(x, cal, p["if_scale"], wr, nr)
+        out["profile_k1"][f] = O.range_profile(X)
+        out["cube_peak"] = max(out["cube_peak"], float(np.abs(X.real).max()) / nr, float(np.abs(X.imag).max()) / nr)
+        if cube_dtype == C32H:
+            X = fp16_round(X, 1.0 / nr)
+        prof = O.range_profile(X)
+        ridx, rmag = O.search_peak(prof, nr, p["range_thr"], M, p["min_d"], p["max_d"], p["dist_per_bin"])
+        rd = O.doppler_all_rows(X, wd, nd)
+        if rd_dtype == C32H:
+            rd = fp16_round(rd, 1.0 / (nr * nd))
+        didx = O.doppler_index(rd, ridx, p["doppler_thr"], p["doppler_fallback_idx"])
+        n = len(ridx)
+        out["profile"][f] = prof
+        out["tgt_count"][f] = n
+        out["tgt_range_idx"][f, :n] = ridx
+        out["tgt_range_mag"][f, :n] = rmag
+        out["tgt_doppler_idx"][f, :n] = didx
+        if n > 0:
+            out["slow_mag"][f] = np.abs(X[ridx[0] - 1, :])
+        out["cube"][f] = X.T
+        out["rd"][f] = rd
+    if probe_column:
+        col = probe_column - 1
+        out["probe"] = np.abs(out["cube"][col // C, col % C, :])
+    return out
+
+
+def rd_err(got, plain) -> np.ndarray:
+    return rd_rel_err(got, plain["rd"], plain["cube"], plain["wd"], plain["rd"].shape[2])
+
+
+def errors(got: dict, plain: dict) -> dict:
+    """Per-frame relative L2 of whatever of KEYS `got` holds against the plain chain ([F] each; the
+    probe column is one frame's, [1])."""
+    e = {}
+    for k in KEYS:
+        if got.get(k) is None:
+            continue
+        if k == "cube":
+            e[k] = rel_l2(got[k], plain[k], axis=(1, 2))
+        elif k == "rd":
+            e[k] = rd_err(got[k], plain)
+        elif k == "probe":
+            e[k] = np.atleast_1d(rel_l2(got[k], plain[k]))
+        else:
+            e[k] = rel_l2(got[k], plain[k], axis=1)
+    return e
+
+
+def bound(e_ref):
+    return np.minimum(2.0 * np.asarray(e_ref) + TOL_FP32_REL_L2, TOL_FP16_REL_L2)
+
+
+def row_gap_ok(plain: dict) -> np.ndarray:
+    """[F][M]: the detected rows of the plain chain whose two largest RD magnitudes differ by more than
+    ROW_GAP relative."""
+    F, M = plain["tgt_range_idx"].shape
+    ok = np.zeros((F, M), bool)
+    for f in range(F):
+        for j in range(int(plain["tgt_count"][f])):
+            mag = np.sort(np.abs(plain["rd"][f, plain["tgt_range_idx"][f, j] - 1]))
+            ok[f, j] = mag[-1] - mag[-2] > ROW_GAP * mag[-1]
+    return ok
+
+
+def near_max_bins(chain: dict, f: int, j: int) -> set:
+    """The 1-based Doppler indices of target j of frame f whose magnitude in `chain` lies within ROW_GAP
+    of the row's maximum.  Where pn is far below nd the zero-padded transform oversamples the row (12
+    chirps into 1024 bins): the bins beside the peak are within 1e-4 of it, the gap rule leaves every
+    row of such a geometry out, and the index is held to this set instead (two fp16 roundings move a
+    magnitude by 2^-10 at the most, below ROW_GAP).  The row peaks of the cases are far from
+    doppler_thr (test_streams_reference_host), so the fallback plays no part."""
+    mag = np.abs(chain["rd"][f, chain["tgt_range_idx"][f, j] - 1])
+    return set((np.nonzero(mag >= mag.max() * (1.0 - ROW_GAP))[0] + 1).tolist())
+
+
+class Ref:
+    """One (geometry, input dtype): the input, the plain chain and the emulated chain per storage pair."""
+
+    def __init__(self, g, in_dtype=C64, kind="synth"):
+        """kind: 'synth' (frame_ids), 'noise' (those and the white frame, last) or 'storage'
+        (storage_frames)."""
+        self.g = g
+        self.cfg, self.p, self.wr, self.wd, self.cal = build_case(g)
+        iq = storage_frames(g, self.cfg) if kind == "storage" else synth(g, self.p)
+        if kind == "noise":
+            iq = np.concatenate([iq, noise_frame(g)])
+        self.F = iq.shape[0]
+        self.noise = self.F - 1 if kind == "noise" else None
+        self.probe_column = min(100, self.F * g[1])
+        self.dev_iq, self.iq = iq_as_stored(iq, in_dtype)
+        self.plain = O.process_frames(self.iq, self.cal, self.p, self.wr, self.wd, want_cube=True, want_rd=True,
+                                      rd_all_rows=True)
+        col = self.probe_column - 1
+        self.plain["probe"] = np.abs(self.plain["cube"][col // g[1], col % g[1], :])
+        self.plain["wd"] = self.wd
+        self._emu = {}
+
+    def emu(self, cube_dtype=C64, rd_dtype=C64) -> dict:
+        key = (cube_dtype, rd_dtype)
+        if key not in self._emu:
+            e = emulate(self.iq, self.cal, self.p, self.wr, self.wd, cube_dtype, rd_dtype, self.probe_column)
+            e["e_ref"] = errors(e, self.plain)
+            self._emu[key] = e
+        return self._emu[key]
+
+    def doppler_mask(self, cube_dtype, rd_dtype) -> np.ndarray:
+        """[F][M]: where tgt_doppler_idx is held exactly -- the emulated and the plain chain agree and
+        the plain row's two largest magnitudes are more than ROW_GAP apart."""
+        e = self.emu(cube_dtype, rd_dtype)
+        used = np.arange(self.plain["tgt_range_idx"].shape[1])[None, :] < self.plain["tgt_count"][:, None]
+        return used & (e["tgt_doppler_idx"] == self.plain["tgt_doppler_idx"]) & row_gap_ok(self.plain)
+
+
+_refs = {}
+
+
+def ref(g, in_dtype=C64, kind="synth") -> Ref:
+    """The reference of a case, computed once per process and shared; never modified by a test."""
+    key = (tuple(g), in_dtype, kind)
+    if key not in _refs:
+        _refs[key] = Ref(g, in_dtype, kind)
+    return _refs[key]
+
+
+def near_ties(r: Ref) -> np.ndarray:
+    return near_tie_frames(r.plain["profile"], rtol=1e-3)
