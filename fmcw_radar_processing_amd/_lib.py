@@ -20,7 +20,7 @@ FMCW_PIPE_AUTO, FMCW_PIPE_STREAMS, FMCW_PIPE_ONEPASS, FMCW_PIPE_XCD = 0, 1, 3, 4
 ABI_VERSION = 4
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_HIP", -3: "E_OOM", -4: "E_STATE", -5: "E_DATA"}
 STAGES = ("range", "doppler", "detect", "compact", "stft_power", "stft_db", "range_only", "range_doppler", "onepass",
-          "render", "cfar", "cluster", "track", "mti")
+          "render", "cfar", "cluster", "track", "mti", "aoa")
 FMCW_CFAR_LOCAL_MAX = 1
 FMCW_SIG_DB = 1
 FMCW_MTI_RAMP, FMCW_MTI_FREEZE = 1, 2
@@ -73,6 +73,22 @@ class Targets(ct.Structure):
 
 TARGET_INT_KEYS = ("cells", "peak_range_idx", "peak_doppler_idx", "extent_r", "extent_d")
 TARGET_FLOAT_KEYS = ("peak_power", "peak_noise", "power", "range", "doppler")
+
+
+class AoaParams(ct.Structure):
+    """fmcw_aoa_params (include/fmcw.h)."""
+    _fields_ = [("n_chan", ct.c_int32), ("max_tgt", ct.c_int32), ("flags", ct.c_int32), ("spacing", ct.c_float),
+                ("w", ct.c_float * 16)]
+
+
+class Angles(ct.Structure):
+    """fmcw_angles (include/fmcw.h): output pointers, det_* [F][max_det], tgt_* [F][max_tgt]."""
+    _fields_ = [(k, ct.c_void_p) for k in ("det_zre", "det_zim", "det_phase", "det_sin", "tgt_zre", "tgt_zim", "tgt_e0",
+                                           "tgt_e1", "tgt_phase", "tgt_sin", "tgt_coh", "tgt_cells")]
+
+
+ANGLE_DET_KEYS = ("det_zre", "det_zim", "det_phase", "det_sin")
+ANGLE_TGT_FLOAT_KEYS = ("tgt_zre", "tgt_zim", "tgt_e0", "tgt_e1", "tgt_phase", "tgt_sin", "tgt_coh")
 
 
 class TrackParams(ct.Structure):
@@ -158,6 +174,11 @@ SIGNATURES = {
                                        ct.POINTER(Targets), _P, _P]),
     "fmcw_cluster": (ct.c_int, [_P, ct.POINTER(ClusterParams), _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P,
                                 ct.POINTER(Targets), _P]),
+    "fmcw_aoa_check": (ct.c_int, [ct.POINTER(AoaParams), _I32, _I32, _I32]),
+    "fmcw_aoa_device": (ct.c_int, [_P, ct.POINTER(AoaParams), ct.POINTER(_P), _I32, _I64, _I32, _I32, _I32, _P, _P, _P, _P,
+                                   ct.POINTER(Angles), _P]),
+    "fmcw_aoa": (ct.c_int, [_P, ct.POINTER(AoaParams), ct.POINTER(_P), _I32, _I64, _I32, _I32, _I32, _P, _P, _P, _P,
+                            ct.POINTER(Angles)]),
     "fmcw_track_check": (ct.c_int, [ct.POINTER(TrackParams), _I32, _I32, _I32]),
     "fmcw_track_state_bytes": (_I32, [_I32]),
     "fmcw_track_device": (ct.c_int, [_P, ct.POINTER(TrackParams), _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P,

@@ -127,7 +127,7 @@ inline void shard(int64_t total, int g, int world, int64_t& f0, int64_t& n) {
   n = base + (g < rem ? 1 : 0);
 }
 
-constexpr int kStages = 14;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar, 11 cluster, 12 track, 13 mti
+constexpr int kStages = 15;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar, 11 cluster, 12 track, 13 mti, 14 aoa
 
 }  // namespace fmcw
 
@@ -256,6 +256,8 @@ struct fmcw_ctx {
   DevBuf sg_in, sg_ctr, sg_out;
   // fmcw_cluster (host pointers): the chunk's detection lists and the per-frame outputs on the device
   DevBuf cl_in, cl_out;
+  // fmcw_aoa (host pointers): the chunk's frames of every channel, the chunk's lists and the per-frame outputs on the device
+  DevBuf ao_rd, ao_in, ao_out;
   // fmcw_track (host pointers): the chunk's target rows, the chunk's outputs and the sequences' state on the device
   DevBuf tk_in, tk_out, tk_state;
   // fmcw_mti (host pointers): the chunk's frames (filtered in place) and the sequences' state on the device

@@ -1,5 +1,6 @@
 // api_stages.cpp -- the RD-map stages of the libfmcw C-ABI (include/fmcw.h): 2-D CA-CFAR,
-// Doppler-time / range-time signatures, clustering, tracking and the MTI clutter filter.
+// Doppler-time / range-time signatures, clustering, angle of arrival, tracking and the MTI clutter
+// filter.
 // Every stage has a host-only fmcw_*_check, a device-pointer entry and a host-pointer entry that
 // shards over the context's devices and walks its shard in chunks; the two entries share the
 // stage's *_entry check.  The rules every stage states alike take the stage's message prefix.
@@ -524,6 +525,189 @@ int fmcw_cluster(fmcw_ctx* c, const fmcw_cluster_params* q, int64_t F, int32_t n
   return over_devices(c, F, [&](fmcw_ctx* d, int, int64_t f0, int64_t n) {
     return cluster_host_one(d, q, n, nr, nd, max_det, count + f0, ridx + f0 * K, didx + f0 * K, power + f0 * K,
                             shifted(noise, f0 * K), offset(*out, f0, M), shifted(label, f0 * K));
+  });
+}
+
+// ---------------------------------------------------------------------------
+// Angle of arrival from several receive channels of the RD map (kernels_aoa.hip)
+// ---------------------------------------------------------------------------
+int fmcw_aoa_check(const fmcw_aoa_params* q, int32_t nr, int32_t nd, int32_t max_det) {
+  if (!q) return fail(FMCW_E_ARG, "aoa params is NULL");
+  CHK(check_rd_shape("aoa", nr, nd));
+  if (q->n_chan < 2 || q->n_chan > fmcw::kAoaChan) return fail(FMCW_E_ARG, "aoa: n_chan must be in [2, 8]");
+  if (q->max_tgt < 0 || q->max_tgt > 64) return fail(FMCW_E_ARG, "aoa: max_tgt must be 0 or in [1, 64]");
+  if (max_det < 1 || max_det > 1024) return fail(FMCW_E_ARG, "aoa: max_det must be in [1, 1024]");
+  if (q->flags != 0) return fail(FMCW_E_ARG, "aoa: unknown flag bits");
+  if (!std::isfinite(q->spacing) || !(std::fabs(q->spacing) >= 0.01f && std::fabs(q->spacing) <= 16.f))
+    return fail(FMCW_E_ARG, "aoa: spacing must be finite with 0.01 <= |spacing| <= 16");
+  for (int i = 0; i < 2 * q->n_chan; ++i)
+    if (!std::isfinite(q->w[i])) return fail(FMCW_E_ARG, "aoa: the weights must be finite");
+  return FMCW_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+constexpr int kAoaDet = 4, kAoaOut = 12;   // fmcw_angles: the first kAoaDet members are per cell, the rest per target
+
+// the members of an fmcw_angles in declaration order
+void aoa_members(const fmcw_angles& t, void* (&m)[kAoaOut]) {
+  void* const v[kAoaOut] = {t.det_zre, t.det_zim, t.det_phase, t.det_sin, t.tgt_zre, t.tgt_zim,
+                            t.tgt_e0,  t.tgt_e1,  t.tgt_phase, t.tgt_sin, t.tgt_coh, t.tgt_cells};
+  for (int i = 0; i < kAoaOut; ++i) m[i] = v[i];
+}
+
+// t moved on by `rows` frames of K cells and M targets
+fmcw_angles offset(const fmcw_angles& t, int64_t rows, int64_t K, int64_t M) {
+  const int64_t k = rows * K, m = rows * M;
+  fmcw_angles o{};
+  o.det_zre = shifted(t.det_zre, k); o.det_zim = shifted(t.det_zim, k);
+  o.det_phase = shifted(t.det_phase, k); o.det_sin = shifted(t.det_sin, k);
+  o.tgt_zre = shifted(t.tgt_zre, m); o.tgt_zim = shifted(t.tgt_zim, m);
+  o.tgt_e0 = shifted(t.tgt_e0, m); o.tgt_e1 = shifted(t.tgt_e1, m);
+  o.tgt_phase = shifted(t.tgt_phase, m); o.tgt_sin = shifted(t.tgt_sin, m);
+  o.tgt_coh = shifted(t.tgt_coh, m); o.tgt_cells = shifted(t.tgt_cells, m);
+  return o;
+}
+
+// what both angle entries check before they look at F == 0 and the input pointers
+int aoa_entry(fmcw_ctx* c, const fmcw_aoa_params* q, int32_t rd_dtype, int64_t F, int32_t nr, int32_t nd, int32_t max_det,
+              const int32_t* label, const fmcw_angles* out) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(fmcw_aoa_check(q, nr, nd, max_det));
+  CHK(check_rd_dtype(rd_dtype));
+  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
+  if (!out) return fail(FMCW_E_ARG, "aoa: the output struct is NULL");
+  void* m[kAoaOut];
+  aoa_members(*out, m);
+  bool any = false, tgt = false;
+  for (int i = 0; i < kAoaOut; ++i) {
+    any = any || m[i];
+    tgt = tgt || (i >= kAoaDet && m[i]);
+  }
+  if (!any) return fail(FMCW_E_ARG, "aoa: every output is NULL");
+  if (tgt && !label) return fail(FMCW_E_ARG, "aoa: a per-target output needs det_label");
+  if (tgt && q->max_tgt == 0) return fail(FMCW_E_ARG, "aoa: a per-target output needs max_tgt >= 1");
+  return FMCW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fmcw_aoa_device(fmcw_ctx* c, const fmcw_aoa_params* q, const void* const* d_rd_ch, int32_t rd_dtype, int64_t F,
+                    int32_t nr, int32_t nd, int32_t max_det, const int32_t* d_count, const int32_t* d_ridx,
+                    const int32_t* d_didx, const int32_t* d_label, const fmcw_angles* d_out, void* stream) {
+  CHK(aoa_entry(c, q, rd_dtype, F, nr, nd, max_det, d_label, d_out));
+  if (F == 0) return FMCW_OK;
+  if (!d_rd_ch || !d_count || !d_ridx || !d_didx) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const int A = q->n_chan;
+  for (int ch = 0; ch < A; ++ch) {
+    if (!d_rd_ch[ch]) return fail(FMCW_E_ARG, "required pointer is NULL");
+    if (reinterpret_cast<uintptr_t>(d_rd_ch[ch]) & 15) return fail(FMCW_E_ARG, "aoa: every channel's d_rd must be 16-byte aligned");
+  }
+  CHK(set_device(c));
+  hipStream_t s = pick(c, stream);
+  fmcw::AoaArgs a{};
+  a.NR = nr; a.ND = nd;
+  a.K = max_det;
+  a.A = A;
+  a.M = q->max_tgt;
+  a.h = rd_dtype == FMCW_C32H;
+  a.scale2 = a.h ? ((float)nr * (float)nd) * ((float)nr * (float)nd) : 1.f;
+  a.kinv = (float)(1.0 / (2.0 * 3.14159265358979323846 * (double)q->spacing));
+  for (int i = 0; i < 2 * A; ++i) a.w[i] = q->w[i];
+  a.tgt_any = d_out->tgt_zre || d_out->tgt_zim || d_out->tgt_e0 || d_out->tgt_e1 || d_out->tgt_phase ||
+              d_out->tgt_sin || d_out->tgt_coh || d_out->tgt_cells;
+  const int64_t K = max_det, M = q->max_tgt;
+  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
+  // one workgroup per frame: at most 2^20 frames per launch (the results do not depend on the cut)
+  const int64_t Fc = (int64_t)1 << 20;
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    a.F = std::min(Fc, F - f0);
+    for (int ch = 0; ch < A; ++ch) a.rd[ch] = static_cast<const char*>(d_rd_ch[ch]) + (size_t)f0 * fin;
+    a.det_count = d_count + f0;
+    a.det_ridx = d_ridx + f0 * K;
+    a.det_didx = d_didx + f0 * K;
+    a.det_label = shifted(d_label, f0 * K);
+    const fmcw_angles t = offset(*d_out, f0, K, M);
+    a.det_zre = t.det_zre; a.det_zim = t.det_zim; a.det_phase = t.det_phase; a.det_sin = t.det_sin;
+    a.tgt_zre = t.tgt_zre; a.tgt_zim = t.tgt_zim; a.tgt_e0 = t.tgt_e0; a.tgt_e1 = t.tgt_e1;
+    a.tgt_phase = t.tgt_phase; a.tgt_sin = t.tgt_sin; a.tgt_coh = t.tgt_coh; a.tgt_cells = t.tgt_cells;
+    StageTimer tm(c, 14, s);
+    HIPCHK(fmcw::launch_aoa(a, s));
+    tm.done();
+  }
+  return FMCW_OK;
+}
+
+static int aoa_host_one(fmcw_ctx* c, const fmcw_aoa_params* q, const char* const* rd_ch, int32_t dtype, int64_t F, int32_t nr,
+                        int32_t nd, int32_t K, const int32_t* count, const int32_t* ridx, const int32_t* didx,
+                        const int32_t* label, const fmcw_angles& out) {
+  CHK(set_device(c));
+  hipStream_t s = c->stream;
+  const int A = q->n_chan, M = q->max_tgt;
+  const size_t fin = (size_t)nr * nd * esize(dtype), flist = (size_t)K * 4;
+  // all A channels of a chunk are staged
+  const int64_t Fc = host_chunk((size_t)A * fin, F);
+  // the shard's outputs in the context's ao_out: the fmcw_angles members in declaration order
+  void* host[kAoaOut];
+  aoa_members(out, host);
+  Arena in, ou;
+  size_t oo[kAoaOut], obytes[kAoaOut];
+  for (int i = 0; i < kAoaOut; ++i) oo[i] = ou.add(obytes[i] = (size_t)F * 4 * (i < kAoaDet ? K : M));
+  const size_t i_count = in.add((size_t)Fc * 4), i_ridx = in.add((size_t)Fc * flist), i_didx = in.add((size_t)Fc * flist),
+               i_label = in.add((size_t)Fc * flist);
+  CHK(c->ao_out.ensure(ou.off));
+  CHK(c->ao_in.ensure(in.off));
+  CHK(c->ao_rd.ensure((size_t)A * Fc * fin));
+  char* const o = c->ao_out.as<char>();
+  char* const di = c->ao_in.as<char>();
+  char* const dr = c->ao_rd.as<char>();
+  const void* d_ch[fmcw::kAoaChan] = {};
+  for (int ch = 0; ch < A; ++ch) d_ch[ch] = dr + (size_t)ch * Fc * fin;   // a multiple of 256 bytes apart
+  const fmcw_angles dev{dev_of(out.det_zre, o, oo[0]), dev_of(out.det_zim, o, oo[1]), dev_of(out.det_phase, o, oo[2]),
+                        dev_of(out.det_sin, o, oo[3]), dev_of(out.tgt_zre, o, oo[4]), dev_of(out.tgt_zim, o, oo[5]),
+                        dev_of(out.tgt_e0, o, oo[6]), dev_of(out.tgt_e1, o, oo[7]), dev_of(out.tgt_phase, o, oo[8]),
+                        dev_of(out.tgt_sin, o, oo[9]), dev_of(out.tgt_coh, o, oo[10]), dev_of(out.tgt_cells, o, oo[11])};
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    const int64_t nf = std::min(Fc, F - f0);
+    for (int ch = 0; ch < A; ++ch)
+      HIPCHK(hipMemcpyAsync(dr + (size_t)ch * Fc * fin, rd_ch[ch] + (size_t)f0 * fin, (size_t)nf * fin, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(di + i_count, count + f0, (size_t)nf * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(di + i_ridx, ridx + f0 * K, (size_t)nf * flist, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(di + i_didx, didx + f0 * K, (size_t)nf * flist, hipMemcpyHostToDevice, s));
+    if (label) HIPCHK(hipMemcpyAsync(di + i_label, label + f0 * K, (size_t)nf * flist, hipMemcpyHostToDevice, s));
+    const fmcw_angles d = offset(dev, f0, K, M);
+    CHK(fmcw_aoa_device(c, q, d_ch, dtype, nf, nr, nd, K, reinterpret_cast<int32_t*>(di + i_count),
+                        reinterpret_cast<int32_t*>(di + i_ridx), reinterpret_cast<int32_t*>(di + i_didx),
+                        label ? reinterpret_cast<int32_t*>(di + i_label) : nullptr, &d, s));
+    HIPCHK(hipStreamSynchronize(s));           // the chunk buffers are reused by the next chunk
+  }
+  for (int i = 0; i < kAoaOut; ++i)
+    if (host[i]) HIPCHK(hipMemcpyAsync(host[i], o + oo[i], obytes[i], hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return FMCW_OK;
+}
+
+int fmcw_aoa(fmcw_ctx* c, const fmcw_aoa_params* q, const void* const* rd_ch, int32_t rd_dtype, int64_t F, int32_t nr,
+             int32_t nd, int32_t max_det, const int32_t* count, const int32_t* ridx, const int32_t* didx,
+             const int32_t* label, const fmcw_angles* out) {
+  CHK(aoa_entry(c, q, rd_dtype, F, nr, nd, max_det, label, out));
+  if (F == 0) return FMCW_OK;
+  if (!rd_ch || !count || !ridx || !didx) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const int A = q->n_chan;
+  for (int ch = 0; ch < A; ++ch)
+    if (!rd_ch[ch]) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
+  const int64_t K = max_det, M = q->max_tgt;
+  // frames are independent: contiguous shards, each written in place
+  return over_devices(c, F, [&](fmcw_ctx* d, int, int64_t f0, int64_t n) {
+    const char* ch0[fmcw::kAoaChan] = {};
+    for (int ch = 0; ch < A; ++ch) ch0[ch] = static_cast<const char*>(rd_ch[ch]) + (size_t)f0 * fin;
+    return aoa_host_one(d, q, ch0, rd_dtype, n, nr, nd, max_det, count + f0, ridx + f0 * K, didx + f0 * K,
+                        shifted(label, f0 * K), offset(*out, f0, K, M));
   });
 }
 

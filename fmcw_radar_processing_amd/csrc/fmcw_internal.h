@@ -363,6 +363,32 @@ struct ClusterArgs {
 };
 hipError_t launch_cluster(const ClusterArgs& a, hipStream_t s);
 
+// Angle of arrival from several receive channels' RD maps at the CFAR cells (kernels_aoa.hip): k_aoa
+constexpr int kAoaChan = 8;            // channels at most
+struct AoaArgs {
+  int64_t F;
+  int NR, ND;
+  int K;                   // max_det: entries per frame of the lists
+  int A;                   // channels, 2..kAoaChan
+  int M;                   // max_tgt, 0: no per-target outputs
+  int h;                   // fp16 storage
+  int tgt_any;             // some per-target output is asked for (then det_label is set and M >= 1)
+  float scale2;            // (NR * ND)^2 when h, else 1: z, e0, e1 come out in the units of |D|^2
+  float kinv;              // 1 / (2 pi spacing)
+  float w[2 * kAoaChan];   // the channels' complex weights (re, im)
+  const void* rd[kAoaChan];        // channel a: [F][NR][ND] c64, or c32h (h) holding D / (NR ND)
+  const int32_t* det_count;        // [F]
+  const int32_t* det_ridx;         // [F][K]
+  const int32_t* det_didx;         // [F][K]
+  const int32_t* det_label;        // [F][K] or nullptr
+  // [F][K] each, any may be nullptr
+  float* det_zre; float* det_zim; float* det_phase; float* det_sin;
+  // [F][M] each, any may be nullptr
+  float* tgt_zre; float* tgt_zim; float* tgt_e0; float* tgt_e1; float* tgt_phase; float* tgt_sin; float* tgt_coh;
+  int32_t* tgt_cells;
+};
+hipError_t launch_aoa(const AoaArgs& a, hipStream_t s);
+
 // Tracking of the per-frame targets across frames (kernels_track.hip): k_track
 // One sequence's state block: kTrackFields arrays of T = max_trk 32-bit words (id, status, hits,
 // misses, age as int32; r, v, d, power as float32), then the id counter, padded to 16 bytes.

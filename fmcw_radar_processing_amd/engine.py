@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import FMCW_C32H, FMCW_C64, STAGES, FmcwError, check
-from .params import CfarConfig, ClusterConfig, FmcwConfig, MtiConfig, SigConfig, TrackConfig
+from .params import AoaConfig, CfarConfig, ClusterConfig, FmcwConfig, MtiConfig, SigConfig, TrackConfig
 
 
 def _ptr(a) -> ct.c_void_p:
@@ -438,6 +438,73 @@ class Engine:
                                  d_cube=d_cube, probe_column=probe_column, stream=stream)
         self.cluster_device(q_cluster, F, cfg.nr, cfg.nd, q_cfar.max_det, cfar_outs, tgt_outs,
                             d_det_label=d_det_label, stream=stream)
+
+    # ---- angle of arrival from several receive channels (include/fmcw.h, fmcw_aoa_params) -----
+    def aoa(self, rds, det: dict, q: AoaConfig, labels: np.ndarray | None = None) -> dict:
+        """Angles at the cells of the detection lists `det` (the dict Engine.cfar returns) from the
+        q.n_chan RD maps `rds`, one per receive channel, each complex64 [F][nr][nd] or float16
+        [F][nr][nd][2] holding D / (nr nd), all of one dtype and shape.  labels: det_label
+        [F][max_det] of Engine.cluster, needed for the per-target outputs (without it, or with
+        q.max_tgt 0, only the per-cell ones are returned).  Host arrays, sharded over the context's
+        devices.  Returns det_zre, det_zim, det_phase, det_sin [F][max_det] and tgt_zre, tgt_zim,
+        tgt_e0, tgt_e1, tgt_phase, tgt_sin, tgt_coh (float32), tgt_cells (int32) [F][max_tgt], 0
+        where unused."""
+        chans = [_host_rd(rd, "F") for rd in rds]
+        if len(chans) != int(q.n_chan):
+            raise ValueError("aoa: rds must hold q.n_chan maps")
+        dt = chans[0][1]
+        if any(c[1] != dt or c[0].shape != chans[0][0].shape for c in chans):
+            raise ValueError("aoa: the channels must share one dtype and shape")
+        F, nr, nd = chans[0][0].shape[:3]
+        cnt = np.ascontiguousarray(det["det_count"], np.int32)
+        ridx = np.ascontiguousarray(det["det_range_idx"], np.int32)
+        didx = np.ascontiguousarray(det["det_doppler_idx"], np.int32)
+        if cnt.shape != (F,) or ridx.ndim != 2 or ridx.shape[0] != F or didx.shape != ridx.shape:
+            raise ValueError("the detection lists must be [F][max_det], det_count [F]")
+        K, M = ridx.shape[1], int(q.max_tgt)
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, np.int32)
+            if labels.shape != ridx.shape:
+                raise ValueError("labels must be [F][max_det]")
+        out = {k: np.zeros((F, K), np.float32) for k in _lib.ANGLE_DET_KEYS}
+        if labels is not None and M > 0:
+            for k in _lib.ANGLE_TGT_FLOAT_KEYS:
+                out[k] = np.zeros((F, M), np.float32)
+            out["tgt_cells"] = np.zeros((F, M), np.int32)
+        qa = q.abi()
+        ptrs = (ct.c_void_p * len(chans))(*[c[0].ctypes.data for c in chans])
+        t = _lib.Angles(*[_ptr(out.get(k)) for k, _ in _lib.Angles._fields_])
+        check(self.lib.fmcw_aoa(self.h, ct.byref(qa), ptrs, dt, F, nr, nd, K, _ptr(cnt), _ptr(ridx), _ptr(didx),
+                                _ptr(labels), ct.byref(t)))
+        return out
+
+    def aoa_device(self, q: AoaConfig, d_rds, rd_dtype: int, F: int, nr: int, nd: int, max_det: int, det: dict,
+                   outs: dict, d_det_label=None, stream=None) -> None:
+        """fmcw_aoa_device: d_rds the q.n_chan device RD maps [F][nr][nd] of rd_dtype (separate
+        allocations or slices of one, each 16-byte aligned); det the device buffers fmcw_cfar_device
+        wrote (det_count, det_range_idx, det_doppler_idx); outs any of the device buffers det_zre,
+        det_zim, det_phase, det_sin [F][max_det] and tgt_zre, tgt_zim, tgt_e0, tgt_e1, tgt_phase,
+        tgt_sin, tgt_coh (float32), tgt_cells (int32) [F][max_tgt] (missing or None: not written);
+        d_det_label [F][max_det] int32 of fmcw_cluster_device, needed by the tgt_* outputs.  q: an
+        AoaConfig, or the C struct _lib.AoaParams itself.  Asynchronous on `stream`."""
+        qa = q.abi() if hasattr(q, "abi") else q
+        ptrs = (ct.c_void_p * len(d_rds))(*[_ptr(d).value or 0 for d in d_rds])
+        t = _lib.Angles(*[_ptr(outs.get(k)) for k, _ in _lib.Angles._fields_])
+        with _sided(stream) as hs:
+            check(self.lib.fmcw_aoa_device(self.h, ct.byref(qa), ptrs, int(rd_dtype), int(F), int(nr), int(nd),
+                                           int(max_det), _ptr(det["det_count"]), _ptr(det["det_range_idx"]),
+                                           _ptr(det["det_doppler_idx"]), _ptr(d_det_label), ct.byref(t), hs))
+
+    def angles(self, rds, q_cfar: CfarConfig, q_cluster: ClusterConfig, q_aoa: AoaConfig, det_chan: int = 0) -> dict:
+        """cfar on channel det_chan, cluster, then aoa over all channels (host arrays): the three
+        dicts merged, plus angle_deg [F][max_det] and tgt_angle_deg [F][max_tgt], degrees(arcsin(sin))
+        formed on the host."""
+        out = self.targets(rds[det_chan], q_cfar, q_cluster)
+        out.update(self.aoa(rds, out, q_aoa, labels=out["det_label"]))
+        out["angle_deg"] = np.degrees(np.arcsin(out["det_sin"].astype(np.float64)))
+        if "tgt_sin" in out:
+            out["tgt_angle_deg"] = np.degrees(np.arcsin(out["tgt_sin"].astype(np.float64)))
+        return out
 
     # ---- tracks from the per-frame targets (include/fmcw.h, fmcw_track_params) ----------------
     def track_state_bytes(self, max_trk: int) -> int:

@@ -12,8 +12,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import windows
-from ._lib import (FMCW_CFAR_LOCAL_MAX, FMCW_MTI_FREEZE, FMCW_MTI_RAMP, FMCW_SIG_DB, CfarParams, ClusterParams, MtiParams,
-                   Params, SigParams, TrackParams)
+from ._lib import (FMCW_CFAR_LOCAL_MAX, FMCW_MTI_FREEZE, FMCW_MTI_RAMP, FMCW_SIG_DB, AoaParams, CfarParams,
+                   ClusterParams, MtiParams, Params, SigParams, TrackParams)
 
 C0 = 3e8  # radar_processing.m:67
 
@@ -249,6 +249,60 @@ class ClusterConfig:
         q = cls(link_r=int(link[0]), link_d=int(link[1]), min_cells=int(min_cells), max_tgt=int(max_tgt))
         q.validate(cfg.nr, cfg.nd, int(max_det))
         return q
+
+
+@dataclass
+class AoaConfig:
+    """fmcw_aoa_params (include/fmcw.h): angle of arrival from n_chan receive channels' RD maps at the
+    CFAR cells.  spacing is the element spacing in wavelengths (signed: the sign sets which side is
+    positive); weights holds one complex weight per channel (None: 1 for every channel), which absorbs
+    the receive paths' phase and gain mismatch; max_tgt 0 asks for no per-target outputs."""
+    n_chan: int = 2
+    spacing: float = 0.5
+    max_tgt: int = 16
+    weights: tuple | None = None
+
+    def abi(self) -> AoaParams:
+        w = [1.0, 0.0] * 8
+        if self.weights is not None:
+            ws = [complex(x) for x in self.weights]
+            if len(ws) != self.n_chan or len(ws) > 8:
+                raise ValueError("aoa: weights needs one complex value per channel")
+            for i, x in enumerate(ws):
+                w[2 * i], w[2 * i + 1] = x.real, x.imag
+        q = AoaParams(self.n_chan, self.max_tgt, 0, self.spacing)
+        with np.errstate(over="ignore"):
+            q.w[:] = [float(np.float32(x)) for x in w]
+        return q
+
+    @property
+    def kinv(self) -> np.float32:
+        """1 / (2 pi spacing) from the float32 spacing the C struct carries, as the library forms it."""
+        return np.float32(1.0 / (2.0 * np.pi * float(np.float32(self.spacing))))
+
+    def weights_f32(self) -> np.ndarray:
+        """float32 [n_chan][2]: the weights as the C struct carries them."""
+        return np.array(self.abi().w[:2 * self.n_chan], np.float32).reshape(self.n_chan, 2)
+
+    def validate(self, nr: int, nd: int, max_det: int) -> None:
+        """The rules of fmcw_aoa_check, on the float32 values the C struct carries; ValueError naming
+        the first one violated."""
+        if nr < 16 or nr > 2048 or nr & (nr - 1):
+            raise ValueError("aoa: nr must be a power of two in [16, 2048]")
+        if nd < 4 or nd > 1024 or nd & (nd - 1):
+            raise ValueError("aoa: nd must be a power of two in [4, 1024]")
+        if not 2 <= self.n_chan <= 8:
+            raise ValueError("aoa: n_chan must be in [2, 8]")
+        if not 0 <= self.max_tgt <= 64:
+            raise ValueError("aoa: max_tgt must be 0 or in [1, 64]")
+        if not 1 <= max_det <= 1024:
+            raise ValueError("aoa: max_det must be in [1, 1024]")
+        with np.errstate(over="ignore"):
+            sp = np.float32(self.spacing)
+        if not (np.isfinite(sp) and np.float32(0.01) <= abs(sp) <= np.float32(16)):
+            raise ValueError("aoa: spacing must be finite with 0.01 <= |spacing| <= 16")
+        if not np.isfinite(self.weights_f32()).all():
+            raise ValueError("aoa: the weights must be finite")
 
 
 @dataclass

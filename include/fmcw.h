@@ -51,7 +51,9 @@ extern "C" {
  *    fmcw_track), the structs fmcw_track_params / fmcw_tracks and timing stage 12, added within
  *    ABI 4 in the same way
  *    + the clutter-filter entry points (fmcw_mti_check, fmcw_mti_ring, fmcw_mti_device, fmcw_mti),
- *    the struct fmcw_mti_params and timing stage 13, added within ABI 4 in the same way */
+ *    the struct fmcw_mti_params and timing stage 13, added within ABI 4 in the same way
+ *    + the angle-of-arrival entry points (fmcw_aoa_check, fmcw_aoa_device, fmcw_aoa), the structs
+ *    fmcw_aoa_params / fmcw_angles and timing stage 14, added within ABI 4 in the same way */
 #define FMCW_ABI_VERSION 4
 
 typedef enum fmcw_status {
@@ -279,7 +281,8 @@ int fmcw_synth_device(fmcw_ctx* ctx, const fmcw_params* p, int64_t frame0, int64
  *        level 2), 9 render (spectrogram.png), 10 cfar (one pair per k_cfar + k_cfar_gather
  *        launch pair of fmcw_cfar_device), 11 cluster (one pair per k_cluster launch of
  *        fmcw_cluster_device), 12 track (one pair per k_track launch of fmcw_track_device),
- *        13 mti (one pair per fmcw_mti_device call's k_mti + k_mti_seen launches).
+ *        13 mti (one pair per fmcw_mti_device call's k_mti + k_mti_seen launches), 14 aoa (one pair
+ *        per k_aoa launch of fmcw_aoa_device).
  *        fmcw_timing_read synchronises. */
 int fmcw_timing_enable(fmcw_ctx* ctx, int32_t enable);
 int fmcw_timing_read(fmcw_ctx* ctx, int32_t stage, double* total_ms, int64_t* launches);
@@ -532,6 +535,112 @@ int fmcw_cluster_device(fmcw_ctx* ctx, const fmcw_cluster_params* q, int64_t F, 
 int fmcw_cluster(fmcw_ctx* ctx, const fmcw_cluster_params* q, int64_t F, int32_t nr, int32_t nd, int32_t max_det,
                  const int32_t* det_count, const int32_t* det_range_idx, const int32_t* det_doppler_idx,
                  const float* det_power, const float* det_noise, const fmcw_targets* out, int32_t* det_label);
+
+/* ---------------------------------------------------------------------------
+ * Angle of arrival from several receive channels of the RD map (added within ABI 4; beyond the
+ * reference, which parses numAntennasRx, :103, and keeps only frame.Chirp(:,:,1), :202).  For the
+ * cells CFAR found and the targets clustering formed it takes the same cells from every channel's RD
+ * map and turns the inter-channel phase into an angle.  The caller runs fmcw_set_taps + fmcw_process*
+ * once per receive plane (each plane has its own calib_rx); RD -> MTI -> CFAR -> clusters are linear
+ * or work on lists, so the phase relation between the planes' maps survives them.
+ *   Input: A channel maps rd[a], a = 0..A-1, A in 2..8, each [F][nr][nd] in the layout fmcw_process*
+ *     writes, all of one dtype, FMCW_C64 or FMCW_C32H; nr, nd within CFAR's limits.  The maps are
+ *     given as a host array of A pointers (for the device call: device pointers; the array itself is
+ *     read on the host, as fmcw_targets is), each 16-byte aligned; separate allocations or slices of
+ *     one.  The detection lists exactly as fmcw_cfar* writes them: det_count [F], det_range_idx,
+ *     det_doppler_idx [F][max_det], 1-based, max_det in 1..1024; optionally det_label [F][max_det]
+ *     from fmcw_cluster*.  n = clamp(det_count[f], 0, max_det).
+ *     Unlike clustering, the indices ARE used as addresses here: cell i < n is valid iff
+ *     1 <= r <= nr and 1 <= d <= nd.  An invalid cell is never read through, gives zeros and joins no
+ *     target.  Labels are only compared: a valid cell belongs to target t iff det_label == t with
+ *     1 <= t <= max_tgt; a label of 0, a negative one or one above max_tgt belongs to no target.
+ *   Parameters: n_chan = A; max_tgt 0 (no per-target outputs) or 1..64; flags 0; spacing, the element
+ *     spacing in wavelengths, signed (the sign sets which side is positive), finite,
+ *     0.01 <= |spacing| <= 16; w[16], a complex weight (re, im) per channel, finite, which absorbs the
+ *     receive paths' phase and gain mismatch ((1, 0): none; entries of channels >= A are ignored).
+ *     The host forms kinv = (float)(1.0 / (2 pi (double)spacing)).
+ *   One cell, in float32, every operation rounded on its own in the order written (no fused
+ *   multiply-add):
+ *   1. x_a is the stored value of channel a at (r, d); fp16 storage is widened exactly.
+ *      v_a.re = x.re w.re - x.im w.im;  v_a.im = x.re w.im + x.im w.re.
+ *   2. From zr = zi = e0 = e1 = 0, for a = 0..A-2 with p = v_a, q = v_{a+1}:
+ *      zr += (q.re p.re + q.im p.im);  zi += (q.im p.re - q.re p.im);
+ *      e0 += (p.re^2 + p.im^2);        e1 += (q.re^2 + q.im^2).
+ *      So z = sum v_{a+1} conj(v_a), the lag-1 spatial correlation: phase-comparison monopulse for
+ *      A = 2, the power-weighted single-source estimator for a uniform line of A elements.
+ *   3. Per-cell outputs [F][max_det], each optional:
+ *      det_zre, det_zim   zr, zi times scale2, scale2 = ((float)nr (float)nd)^2 for FMCW_C32H and 1
+ *                         otherwise (an exact power of two: the units of |range_Doppler|^2, as fmcw_sig)
+ *      det_phase          atan2f(zi, zr) in (-pi, pi]; 0 when both are 0
+ *      det_sin            clamp(det_phase kinv, -1, 1): sin(theta).  Bearings are unambiguous for
+ *                         |sin(theta)| <= 1 / (2 |spacing|).
+ *   One target: per-target outputs [F][max_tgt], each optional; they need det_label (a per-target
+ *   output without det_label, or with max_tgt = 0, is FMCW_E_ARG).  Z = (sum zr, sum zi, sum e0,
+ *   sum e1) over the target's valid cells in ascending list position, one cell after the other (no
+ *   float atomics: the bits do not depend on the call, on F, on sharding or on chunking).
+ *      tgt_zre, tgt_zim, tgt_e0, tgt_e1   the sums times scale2
+ *      tgt_phase, tgt_sin                 as above, from the unscaled sums
+ *      tgt_coh     min(1, sqrt(zr zr + zi zi) / (sqrt(e0) sqrt(e1))), 0 when e0 or e1 is 0; sqrt and
+ *                  the divide correctly rounded
+ *      tgt_cells   i32: the number of valid member cells
+ *   A target with no valid member gets zeros.  Unused and invalid entries are 0 in every array.  At
+ *   least one output must be non-NULL.
+ *   A non-finite stored value or weight makes that cell's outputs, and its target's, unspecified; it
+ *   touches nothing else and nothing out of bounds.  The call ends for any list, label and count
+ *   bytes.
+ *   The device's atan2f: the largest error seen on one MI355X over every value the tests and the bench
+ *   compare is 1.93 ulp of the float32 result, against float64 atan2 of the same inputs.
+ *   Measured on one MI355X on the CFAR lists of 4096 frames of 1024 x 256, labels from link (1, 1),
+ *   min_cells 2, max_tgt 16, every output written (profiles/aoa_bench.json, 2026-10-20, tree d65bf9b+), A = 2 /
+ *   A = 4: at 12.5 cells per frame (pfa 1e-6, max_det 64) 0.018 / 0.022 ms complex64 and 0.019 / 0.022 ms fp16
+ *   storage; at 476 cells per frame (pfa 1e-3, max_det 1024) 0.113 / 0.174 ms complex64 and 0.113 / 0.187 ms
+ *   fp16 storage; beside 8.35 / 10.18 ms for the fmcw_cfar_device call and 0.018 / 0.208 ms for the
+ *   fmcw_cluster_device call that produced the lists and labels, and 0.005 / 0.034-0.049 ms for
+ *   fmcw_copy_device over the bytes the stage reads and writes, in the same run: 2.9 to 4.8 times the copy's
+ *   time, so the stage MISSES the copy-time yardstick; its time follows the number of gathered values, not
+ *   their bytes.
+ * ------------------------------------------------------------------------- */
+typedef struct fmcw_aoa_params {
+  int32_t n_chan;          /* 2..8 */
+  int32_t max_tgt;         /* 0, or 1..64 */
+  int32_t flags;           /* 0 */
+  float   spacing;         /* wavelengths, signed; 0.01 <= |spacing| <= 16 */
+  float   w[16];           /* (re, im) per channel */
+} fmcw_aoa_params;
+
+/* Output pointers: det_* [F][max_det], tgt_* [F][max_tgt]; any may be NULL, not all. */
+typedef struct fmcw_angles {
+  float*   det_zre;
+  float*   det_zim;
+  float*   det_phase;
+  float*   det_sin;
+  float*   tgt_zre;
+  float*   tgt_zim;
+  float*   tgt_e0;
+  float*   tgt_e1;
+  float*   tgt_phase;
+  float*   tgt_sin;
+  float*   tgt_coh;
+  int32_t* tgt_cells;
+} fmcw_angles;
+
+/* Host only, no context: FMCW_E_ARG (with a message) for any violation of the constraints. */
+int fmcw_aoa_check(const fmcw_aoa_params* q, int32_t nr, int32_t nd, int32_t max_det);
+
+/* Device pointers (d_rd_ch[a] and the members of *d_out are device pointers; the array and the struct
+ * themselves are read on the host), asynchronous on `stream`; needs no fmcw_set_taps.  Acts on the
+ * context's first device.  F = 0 is a no-op.  FMCW_E_ARG is returned before any launch: the outputs
+ * are then untouched.  d_det_label may be NULL. */
+int fmcw_aoa_device(fmcw_ctx* ctx, const fmcw_aoa_params* q, const void* const* d_rd_ch, int32_t rd_dtype,
+                    int64_t F, int32_t nr, int32_t nd, int32_t max_det, const int32_t* d_det_count,
+                    const int32_t* d_det_range_idx, const int32_t* d_det_doppler_idx, const int32_t* d_det_label,
+                    const fmcw_angles* d_out, void* stream);
+
+/* Host pointers: staged (all A channels of a chunk), sharded over the context's devices and chunked
+ * as fmcw_cfar is (bit-identical shards); returns when the outputs are on the host. */
+int fmcw_aoa(fmcw_ctx* ctx, const fmcw_aoa_params* q, const void* const* rd_ch, int32_t rd_dtype, int64_t F,
+             int32_t nr, int32_t nd, int32_t max_det, const int32_t* det_count, const int32_t* det_range_idx,
+             const int32_t* det_doppler_idx, const int32_t* det_label, const fmcw_angles* out);
 
 /* ---------------------------------------------------------------------------
  * Tracks from the per-frame targets: association, alpha-beta filter, ids (added within ABI 4; the

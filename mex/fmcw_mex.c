@@ -42,6 +42,18 @@
  *                                        'cfar' returns them (noise may be []); tcnt is 1 x F, label max_det x F,
  *                                        the others max_tgt x F; range and doppler are the 1-based power-weighted
  *                                        centroids.  Outputs that are not asked for are not computed.
+ *   [zre, zim, phase, sn, tzre, tzim, te0, te1, tphase, tsn, tcoh, tcells] =
+ *       fmcw_mex('aoa', Q, rd4, cnt, ridx, didx[, label])           -> fmcw_aoa: the angle of arrival at the cells
+ *                                        of 'cfar' and the targets of 'cluster' from several receive planes (beyond
+ *                                        the reference, which keeps frame.Chirp(:,:,1) alone); Q: a struct with the
+ *                                        fields max_tgt, flags, spacing of fmcw_aoa_params and, optionally, w: a
+ *                                        double array of 2 A values (re, im per plane; absent: no weighting); rd4:
+ *                                        single complex Nd x Nr x F x A, cat(4, ...) of the planes' RD maps, each
+ *                                        as for 'cfar' (A = size(rd4, 4) is n_chan); cnt 1 x F, ridx, didx max_det
+ *                                        x F as 'cfar' returns them; label max_det x F as 'cluster' returns it, or
+ *                                        absent / [] (then only the first four outputs exist); zre ... sn are
+ *                                        max_det x F, tzre ... tcells max_tgt x F; sn and tsn are sin(theta).
+ *                                        Outputs that are not asked for are not computed.
  *   [kcnt, id, status, age, misses, range, rate, doppler, power, tgt_track, state] =
  *       fmcw_mex('track', Q, tcnt, range, doppler, power, nr, nd, nseq[, state])  -> fmcw_track: the targets of
  *                                        'cluster' tracked across frames (the per-target time series range_speed
@@ -371,6 +383,70 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     t.doppler = (float*)o[10];
     check(fmcw_cluster(g_ctx, &q, F, nr, nd, (int32_t)K, mxGetInt32s(prhs[2]), mxGetInt32s(prhs[3]), mxGetInt32s(prhs[4]),
                        power, noise, &t, (int32_t*)o[11]));
+    return;
+  }
+  if (!strcmp(cmd, "aoa")) {                /* [zre, zim, phase, sn, tzre, ...] = fmcw_mex('aoa', Q, rd4, cnt, ridx, didx[, label]) */
+    if (nrhs != 6 && nrhs != 7) mexErrMsgIdAndTxt("fmcw:arg", "aoa: Q, rd4, cnt, ridx, didx[, label]");
+    const mxArray* s = prhs[1];
+    const mxArray* rd = prhs[2];
+    if (!mxIsStruct(s)) mexErrMsgIdAndTxt("fmcw:arg", "Q must be a struct");
+    if (!mxIsSingle(rd) || !mxIsComplex(rd) || mxGetNumberOfDimensions(rd) != 4)
+      mexErrMsgIdAndTxt("fmcw:arg", "rd4 must be single complex Nd x Nr x F x A");
+    const mwSize* dims = mxGetDimensions(rd);
+    const int32_t nd = (int32_t)dims[0], nr = (int32_t)dims[1];
+    const int64_t F = (int64_t)dims[2];
+    fmcw_aoa_params q;
+    memset(&q, 0, sizeof q);
+    q.n_chan = (int32_t)dims[3];
+    q.max_tgt = (int32_t)field(s, "max_tgt");
+    q.flags = (int32_t)field(s, "flags");
+    q.spacing = (float)field(s, "spacing");
+    for (int i = 0; i < 8; ++i) q.w[2 * i] = 1.f;
+    const mxArray* w = mxGetField(s, 0, "w");
+    if (w && mxGetNumberOfElements(w) > 0) {
+      if (!mxIsDouble(w) || mxIsComplex(w) || q.n_chan < 1 || q.n_chan > 8 || mxGetNumberOfElements(w) != (mwSize)(2 * q.n_chan))
+        mexErrMsgIdAndTxt("fmcw:arg", "Q.w must be a real double array of 2 A values (re, im per plane)");
+      for (int i = 0; i < 2 * q.n_chan; ++i) q.w[i] = (float)mxGetDoubles(w)[i];
+    }
+    if (!mxIsInt32(prhs[3]) || !mxIsInt32(prhs[4]) || !mxIsInt32(prhs[5]))
+      mexErrMsgIdAndTxt("fmcw:arg", "cnt, ridx and didx must be int32");
+    const mwSize K = mxGetM(prhs[4]);
+    check(fmcw_aoa_check(&q, nr, nd, (int32_t)K));   /* before max_tgt and n_chan size anything */
+    const mwSize n = K * (mwSize)F, M = (mwSize)q.max_tgt;
+    if ((int64_t)mxGetNumberOfElements(prhs[3]) != F || mxGetNumberOfElements(prhs[4]) != n || mxGetNumberOfElements(prhs[5]) != n)
+      mexErrMsgIdAndTxt("fmcw:arg", "cnt must be 1 x F, ridx and didx max_det x F");
+    const int32_t* label = NULL;
+    if (nrhs == 7 && mxGetNumberOfElements(prhs[6]) > 0) {
+      if (!mxIsInt32(prhs[6]) || mxGetNumberOfElements(prhs[6]) != n) mexErrMsgIdAndTxt("fmcw:arg", "label must be int32 max_det x F");
+      label = mxGetInt32s(prhs[6]);
+    }
+    const void* chan[8] = {0};
+    for (int a = 0; a < q.n_chan; ++a) chan[a] = mxGetComplexSingles(rd) + (size_t)a * (size_t)F * (size_t)nr * (size_t)nd;
+    /* outputs past nlhs do not exist: their pointers stay NULL and the library leaves them out; the
+     * per-target ones need the labels and max_tgt >= 1 */
+    const int most = label && M > 0 ? 12 : 4;
+    if (nlhs > most) mexErrMsgIdAndTxt("fmcw:arg", "aoa: the per-target outputs need label and max_tgt >= 1");
+    const int want = nlhs > 1 ? nlhs : 1;
+    void* o[12] = {0};
+    for (int i = 0; i < want; ++i) {
+      plhs[i] = mxCreateNumericMatrix(i < 4 ? K : M, (mwSize)F, i == 11 ? mxINT32_CLASS : mxSINGLE_CLASS, mxREAL);
+      o[i] = i == 11 ? (void*)mxGetInt32s(plhs[i]) : (void*)mxGetSingles(plhs[i]);
+    }
+    fmcw_angles t;
+    t.det_zre = (float*)o[0];
+    t.det_zim = (float*)o[1];
+    t.det_phase = (float*)o[2];
+    t.det_sin = (float*)o[3];
+    t.tgt_zre = (float*)o[4];
+    t.tgt_zim = (float*)o[5];
+    t.tgt_e0 = (float*)o[6];
+    t.tgt_e1 = (float*)o[7];
+    t.tgt_phase = (float*)o[8];
+    t.tgt_sin = (float*)o[9];
+    t.tgt_coh = (float*)o[10];
+    t.tgt_cells = (int32_t*)o[11];
+    check(fmcw_aoa(g_ctx, &q, chan, FMCW_C64, F, nr, nd, (int32_t)K, mxGetInt32s(prhs[3]), mxGetInt32s(prhs[4]),
+                   mxGetInt32s(prhs[5]), label, &t));
     return;
   }
   if (!strcmp(cmd, "track")) {              /* [kcnt, id, ...] = fmcw_mex('track', Q, tcnt, range, doppler, power, nr, nd, nseq[, state]) */
