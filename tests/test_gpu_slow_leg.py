@@ -61,6 +61,8 @@ def _check_same(ref, got, cfg):
               "frame_list"):
         np.testing.assert_array_equal(got[k], ref[k], err_msg=k)
     assert got["L"] == ref["L"] == cfg.pn * int((ref["tgt_count"] > 0).sum())
+    # the definition (:257-260), not only k_compact: pins the fused scan of k_detect_1p's last workgroup too
+    np.testing.assert_array_equal(ref["frame_list"], np.nonzero(ref["tgt_count"] > 0)[0])
     assert got["pmax"] == 0.0 and ref["pmax"] == 123.0
 
 
@@ -83,7 +85,10 @@ def _synth(engine, cfg, F, dt=FMCW_C64, frame0=0):
 
 
 @pytest.mark.parametrize("F,chunk,pipe", [(24, 0, FMCW_PIPE_AUTO), (61, 9, FMCW_PIPE_AUTO), (40, 0, FMCW_PIPE_STREAMS),
-                                          (5000, 0, FMCW_PIPE_AUTO), (5000, 2048, FMCW_PIPE_AUTO)])
+                                          (5000, 0, FMCW_PIPE_AUTO), (5000, 2048, FMCW_PIPE_AUTO),
+                                          # the smallest F whose second 4096-frame pass of the fused scan is a
+                                          # partial vector
+                                          (4097, 0, FMCW_PIPE_AUTO)])
 def test_slow_leg_is_process_then_compact(engine, F, chunk, pipe):
     cfg = P.config(3)
     engine.set_taps(cfg, P.synth_calibration(cfg.nts))

@@ -85,6 +85,7 @@ def _power(engine, x, w, noverlap, nfft, *, L=None, max_seg=None, store=True, sl
         d_halo = torch.from_numpy(np.ascontiguousarray(halo, np.float32)).to(dev)
         if halo_len is not None:
             d_hl = torch.tensor([halo_len], dtype=torch.int64, device=dev)
+    t.update(halo=d_halo, halo_len=d_hl)
     engine.stft_power_device(t["slow"], t["flist"], t["len"], pn, t["win"], wlen, noverlap, nfft, FS, max_seg,
                              t["P"] if store else None, t["pmax"], t["nseg"], d_halo=d_halo,
                              n_halo=0 if halo is None else len(halo), d_halo_len=d_hl)
