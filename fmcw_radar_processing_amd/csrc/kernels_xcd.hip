@@ -730,6 +730,16 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
   };
   // D3: :218 (X - mean) .* 2chebwin, :219 DFT16 over i, twiddle W256^(q d0)
   auto d_a = [&](c2 (&xv)[16], c2 mu) __attribute__((always_inline)) {
+    // the :218 mean in two passes.  The X'_k share -X_0's part of the frame (chirp 0 against the others), and
+    // fl(mean X') is off by an ulp of that shared part: against rows that are otherwise small (a frame whose
+    // content sits in chirp 0: X'_k - mean = -X_0 / 256) that was 256 ulp, 1.3e-5 of a group's rows.  The
+    // residues X'_k - mu are exact where the shared part dominates, and their own mean is the correction.
+#pragma unroll
+    for (int i = 0; i < 16; ++i) xv[i] = xv[i] - mu;
+    c2 s2 = (xv[0] + xv[1]) + (xv[2] + xv[3]);
+#pragma unroll
+    for (int i = 4; i < 16; i += 4) s2 += (xv[i] + xv[i + 1]) + (xv[i + 2] + xv[i + 3]);
+    mu = c2{row_sum16(s2.x), row_sum16(s2.y)} * (1.0f / (float)C);
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const f4v wv = L.wdl[g][lane];
@@ -823,7 +833,8 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
   // stores of R(j - 1) returned, and its group loads of frame j - 2 were issued before them
   // (vmcnt retires in order), so every read of frames <= j - 2 is done: kNS >= 2 suffices.
   // The publish wait counts what every path issues after the slot stores: D(j - 3)'s RD stores
-  // (or row peaks); tools/check_vmcnt.py proves it on the built code.  Steps 0-2 and the last two are peeled, every flag a compile-time constant.
+  // (or row peaks); tools/check_vmcnt.py proves it on the built code.  With FULL and three frames or more on the XCD, steps 0-2 and the last two are
+  // peeled, every flag a compile-time constant; every other launch takes the one copy with run-time flags (below).
   constexpr int kRDs = RD ? 16 : 1;                             // D's stores after the slot stores (RD rows / row peak)
   // flags: std::integral_constant (folded: straight-line copies) or bool (the short-launch copy)
   auto body = [&](int j, auto DJ, auto RJ, auto PUB, auto CNT, auto GJ, auto NEXT, auto G16) __attribute__((always_inline)) {
@@ -974,7 +985,13 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
     }
     return;
 #endif
-    if (nj >= 3) {
+    // nts < Nr (FULL false) takes the run-time copy whatever nj is.  Its peeled copies and its run-time copy
+    // did not round alike (measured; most likely a multiply and an add contracted in one copy and not in the
+    // other, the compiler's choice per inlined copy), so a frame's last bits depended on how many frames its
+    // XCD had in the launch: chunks of 3 against 24 frames at nts 126 changed 57 % of the RD map's elements,
+    // 1.5e-7 relative, at nts 1000 17 %.  FULL's copies agree bit for bit (tests/test_gpu_xcd_grid.py holds
+    // both to that).  The masked form also spilled 23-31 registers with its peeled copies, and spills at most one without them.
+    if (FULL && nj >= 3) {
       //   j       DJ   RJ   PUB  CNT                              GJ   NEXT
       body(0,      F_{}, T_{}, F_{}, C0{},                          F_{}, T_{}, G16);
       body(1,      F_{}, T_{}, T_{}, C1{},                          T_{}, T_{}, G16);
@@ -983,8 +1000,8 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
       body(nj,     T_{}, F_{}, T_{}, CF{},                          T_{}, F_{}, G16);
       body(nj + 1, T_{}, F_{}, F_{}, C0{},                          F_{}, F_{}, G16);
     } else {
-      // 1-2 frames on this XCD (launches of < 24 frames): one copy with run-time flags, every
-      // publish waiting for everything
+      // 1-2 frames on this XCD (launches of < 24 frames), or nts < Nr at any frame count: one copy
+      // with run-time flags, every publish waiting for everything
       for (int j = 0; j < nj + 2; ++j)
         body(j, j >= 2, j < nj, j >= 1 && j - 1 < nj, C0{}, j >= 1 && j - 1 < nj, j + 1 < nj, G16);
     }
