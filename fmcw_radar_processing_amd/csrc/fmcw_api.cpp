@@ -493,10 +493,6 @@ static int build_xcd_tab(fmcw_ctx* c, hipStream_t s) {
       for (int e = 0; e < 2; ++e) xput(fmcw::XT_R1 + (2 * (k1 - 1) + e) * 64 + l, (2 * l + e) * k1);   // W1024^(a k1)
     for (int s1 = 1; s1 < 16; ++s1) xput(fmcw::XT_R2 + (s1 - 1) * 64 + l, 8 * ((l & 7) * s1));      // W128^(a0 s1)
     for (int d0 = 1; d0 < 16; ++d0) xput(fmcw::XT_D1 + (d0 - 1) * 64 + l, 4 * ((l & 15) * d0));     // W256^(q d0)
-    // half-frame build (-DXK_HALF)
-    for (int k1 = 1; k1 < 8; ++k1) xput(fmcw::XT_H1 + (k1 - 1) * 64 + l, 2 * l * k1);              // W512^(l k1)
-    for (int s1 = 1; s1 < 8; ++s1) xput(fmcw::XT_H2 + (s1 - 1) * 64 + l, 16 * ((l & 7) * s1));     // W64^(l0 s1)
-    for (int s2 = 0; s2 < 8; ++s2) xput(fmcw::XT_HC + s2 * 64 + l, l + 64 * s2);                   // W1024^(l + 64 s2)
   }
   CHK(c->x_tab.ensure(xt.size() * 4));
   HIPCHK(hipMemcpyAsync(c->x_tab.p, xt.data(), xt.size() * 4, hipMemcpyHostToDevice, s));
@@ -539,7 +535,7 @@ struct SlowLeg {
 // handed between the CUs of one XCD; k_detect_1p runs the detection (and
 // recomputes the rare slow-time row that was not among a group's candidates).
 // Chunks bound the candidate scratch (XCD_TILES * XCD_CAND rows of PN floats per
-// frame).  The hand-off ring has XCD_MAX_SLOTS slots per XCD.
+// frame).  The hand-off is one 2 MiB slot per XCD, rewritten in place every frame.
 static int process_onepass(fmcw_ctx* c, const fmcw_params* p, const void* d_iq, int h, int64_t F, float* d_prof,
                            int32_t* d_count, int32_t* d_ridx, float* d_rmag, int32_t* d_didx, float* d_slow,
                            void* d_rd, int64_t probe_column, float* d_probe, const SlowLeg* leg, hipStream_t s) {
@@ -547,7 +543,7 @@ static int process_onepass(fmcw_ctx* c, const fmcw_params* p, const void* d_iq, 
   const int64_t chunk = std::min<int64_t>(F, c->chunk_frames > 0 ? c->chunk_frames : 8192);
   const int tiles = fmcw::XCD_TILES, ncand = fmcw::XCD_CAND;
   const int TC = tiles * ncand;
-  const int slots = fmcw::XCD_MAX_SLOTS;
+  const int slots = 1;   // one in-place hand-off slot per XCD (xcd_place, fmcw_internal.h)
   {
 #ifdef FMCW_XCUBE_PAD_AB   // A/B (tools/place_probe.py slots): the slot ring FMCW_XCUBE_PAD bytes into a larger buffer
     CHK(c->x_cube.ensure((size_t)8 * slots * fmcw::XCD_TILES * C * 32 * 8 + ((size_t)1 << 30)));

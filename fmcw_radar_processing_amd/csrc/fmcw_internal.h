@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "xcd_place.h"   // k_rdx's hand-off place map (no HIP types: tests/native/xcd_place.cpp reads it on the host)
+
 namespace fmcw {
 
 // Flags of the events that only order work on one device (stream joins, per-stream scratch
@@ -102,7 +104,7 @@ struct OnePassArgs {
   unsigned long long* clk; // or nullptr: {shader clock, 100 MHz clock} at the start and the end of team 0's
                            // member 0 (k_rdx's effective clock, fmcw_rdx_clock)
   // XCD-team schedule (k_rdx) only:
-  float2* xcube;           // [8 XCDs][slots][XCD_TILES groups][C][32] range-cube hand-off slots
+  float2* xcube;           // [8 XCDs][slots] hand-off slots of 32 x 32 places (xcd_place.h), 2 MiB each
   unsigned* xctr;          // [8 XCDs][2: ready, (unused)][XCD_MAX_SLOTS][32] + [8][32] tickets + the abort word:
                            // one 128-byte line per counter, XCD_CTR_WORDS in all (zero when a launch starts)
   unsigned* xclr;          // the context's other counter set (launches alternate between two): k_rdx's block 0
@@ -111,7 +113,7 @@ struct OnePassArgs {
   unsigned* xerr;          // sticky, reported by fmcw_synchronize: bit 0 a hand-off wait timed out, bit 1 an XCD
                            // got more than 32 blocks (the launch's own abort word lets its grid drain; a later
                            // launch starts with a clear one)
-  int slots;               // hand-off slots allocated per XCD (XCD_MAX_SLOTS; k_rdx uses 2 of them)
+  int slots;               // hand-off slots allocated per XCD (1: k_rdx rewrites one slot in place)
   unsigned s16mask;        // fp16 storage only: bit b set = range bins 128 b .. 128 b + 127 (groups 4 b .. 4 b + 3)
                            // are handed over as c32h (X / NR): no bin of the block can become a detection or
                            // slow-time candidate (host_s16mask in fmcw_api.cpp); 0 = every group c64
@@ -135,17 +137,12 @@ constexpr int XCD_ABORT = XCD_TICKETS + 8 * 32;           // xctr offset of the 
 constexpr int XCD_IDLE = XCD_ABORT + 32;                  // xctr offset of [256 CUs][32] words the non-publishing
                                                           // waves add 0 to (kernels_xcd.hip, publish)
 constexpr int XCD_CTR_WORDS = XCD_IDLE + 256 * 32;
+// (where a chunk of the cube lives in the hand-off slot: xcd_place(j, r, w) of xcd_place.h, included above)
 // table sections (float2, [..][64 lanes])
 constexpr int XT_R1 = 0;             // [14]: W1024^((2l + e) k1), index 2 (k1 - 1) + e
 constexpr int XT_R2 = 14 * 64;       // [15]: W128^((l & 7) s1), s1 = 1..15
 constexpr int XT_D1 = 29 * 64;       // [15]: W256^((l & 15) d0), d0 = 1..15
-// the half-frame hand-off build (-DXK_HALF, kernels_xcd.hip): a wave pair per chirp, each wave a
-// 512-point FFT of the even (odd) samples, combined across the pair
-constexpr int XT_H1 = 44 * 64;       // [7]: W512^(l k1), k1 = 1..7
-constexpr int XT_H2 = 51 * 64;       // [7]: W64^((l & 7) s1), s1 = 1..7
-constexpr int XT_HC = 58 * 64;       // [8]: W1024^(l + 64 s2), s2 = 0..7
-constexpr int XT_SIZE = 66 * 64;
-#ifndef XK_HALF
+constexpr int XT_SIZE = 44 * 64;
 // group g, position p (0..31) <-> range bin: r = k1 + 16 h + 8 e + 128 s2 with
 // k1 = (p >> 3) + 4 (g & 1), h = p & 7, e = (g >> 1) & 1, s2 = g >> 2
 __host__ __device__ inline int xcd_bin(int g, int p) {
@@ -153,12 +150,6 @@ __host__ __device__ inline int xcd_bin(int g, int p) {
 }
 __host__ __device__ inline int xcd_group(int r) { return ((r >> 2) & 1) | (((r >> 3) & 1) << 1) | ((r >> 7) << 2); }
 __host__ __device__ inline int xcd_pos(int r) { return ((r & 3) << 3) | ((r >> 4) & 7); }
-#else
-// half-frame build: group g holds bins 32 g .. 32 g + 31 in order
-__host__ __device__ inline int xcd_bin(int g, int p) { return 32 * g + p; }
-__host__ __device__ inline int xcd_group(int r) { return r >> 5; }
-__host__ __device__ inline int xcd_pos(int r) { return r & 31; }
-#endif
 
 struct Detect1pArgs {
   const float* profile;    // [F][NR]

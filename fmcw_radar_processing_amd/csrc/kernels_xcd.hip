@@ -18,14 +18,21 @@
 // land on XCD x (HW_REG_XCC_ID; xcd_census checks the 32-per-XCD deal and the occupancy
 // before the schedule is enabled) form its team, members k = 0..31 by ticket, and take
 // frames x + 8 j.  Step j publishes R(j-1), runs R(j) and D(j-2) (the Doppler two steps
-// behind, see the step loop); a ring of kNS = 2 slots of 2 MiB per XCD with one ready counter
-// each: D(j-2) reads group k of frame j-2's slot once all 32 members published it.
+// behind, see the step loop); one slot of 2 MiB per XCD, rewritten in place every frame, and two
+// ready counters used in turn: D(j-2) reads group k of frame j-2 once all 32 members published it.
+//
+// The slot is 32 x 32 places of 2 KiB (xcd_place.h): chunk (r, w), the 8 chirps of writer member w
+// for reader member r, sits at place 32 r + w on even team steps and at 32 w + r on odd ones.  The
+// rows a wave stores for frame j + 1 are then exactly the rows it loaded of frame j, and nobody
+// else reads them: the write-after-read hazard of rewriting the slot is wave-local (the wave
+// waits for its own group loads before its slot stores) and costs no team synchronisation.  One
+// slot instead of a ring of two halves the footprint the hand-off holds in the XCD's L2
+// (DESIGN.md 4.0).
 //
 // Hand-off protocol: producers store the slot with plain buffer stores (write-back in the
-// XCD's L2: a line rewritten while resident never leaves it, tools/r04_probe.hip part C; the
-// 2-slot ring competes with the input and RD lines, so about half its lines are written back
-// and re-read through the fabric), `s_waitcnt vmcnt` in every wave, a
-// workgroup barrier, then one agent-scope atomic add on the slot's ready counter.
+// XCD's L2: a line rewritten while resident never leaves it, tools/r04_probe.hip part C),
+// `s_waitcnt vmcnt` in every wave, a workgroup barrier, then one agent-scope atomic add on the
+// frame's ready counter.
 // Consumers poll with scalar loads that miss the scalar cache (s_load glc), then read the
 // slot with buffer_load sc1, which bypasses the CU's L1 and is served by the XCD's L2.
 // Producer and consumer are on the same XCD, so no L2 write-back is needed for visibility.
@@ -73,13 +80,7 @@ using namespace op;
 #define XK_RD_AUX 2                    // RD store cache policy: nt (A/B: 16 = sc1, 17 = sc0 sc1, 18 = sc1 nt, 3 = sc0 nt)
 #endif
 constexpr int kRdAux = XK_RD_AUX;
-#ifndef XK_LAG
-#define XK_LAG 1                       // A/B: the group polled and loaded in step j is frame j - XK_LAG
-#endif
-#ifndef XK_NS
-#define XK_NS (2 * XK_LAG)
-#endif
-constexpr int kLag = XK_LAG;
+constexpr int kLag = 1;                // the group polled and loaded in step j is frame j - kLag
 #ifndef XK_POLLAT
 #define XK_POLLAT 2                    // where wave 0 first polls ready(j - lag) in the step (see the step loop;
                                        // round 6: 2 -- after R1 and the next frame's loads -- is 3-5 % faster than 0)
@@ -87,9 +88,8 @@ constexpr int kLag = XK_LAG;
 #ifndef XK_SKEW_STEPS
 #define XK_SKEW_STEPS 256
 #endif
-static_assert(kLag == 1 || kLag == 2, "poll lag 1 (shipped) or 2");
-constexpr int kNS = XK_NS;            // hand-off slots in use per XCD (2..XCD_MAX_SLOTS; see the step loop)
-static_assert(kNS >= 2 * kLag && kNS <= 4, "slot reuse: seeing ready(j - lag) proves frame j - 2 lag read");
+constexpr int kNS = 2;                 // ready counters used in turn per XCD (frame j counts in counter j % kNS)
+static_assert(kNS >= 2 && kNS <= XCD_MAX_SLOTS, "a counter is reused only after every member has seen its last value");
 constexpr int NK = 32;                 // team members (CUs) per XCD
 constexpr int C = 256;                 // chirps = Doppler points
 constexpr int NW = 8;                  // waves per workgroup = chirps per member
@@ -97,6 +97,11 @@ constexpr int GP = 32;                 // bins per group
 typedef unsigned u2v __attribute__((ext_vector_type(2)));
 typedef unsigned u4v __attribute__((ext_vector_type(4)));
 static_assert(NK * NW == C && NK * GP == NR && NK == XCD_TILES, "team geometry");
+static_assert(NK * NK * XCD_PLACE_BYTES == NK * C * GP * 8 && NW * XCD_ROW_BYTES == XCD_PLACE_BYTES && GP * 8 == XCD_ROW_BYTES,
+              "the slot is 32 x 32 places of 8 rows");
+static_assert(xcd_place(0, 3, 5) == 3 * xcd_place(0, 1, 0) + 5 * xcd_place(0, 0, 1) &&
+              xcd_place(1, 3, 5) == 3 * xcd_place(1, 1, 0) + 5 * xcd_place(1, 0, 1) && xcd_place(0, 0, 0) == 0 && xcd_place(1, 0, 0) == 0,
+              "k_rdx addresses a place by two strides");
 
 struct LdsX {
   union {
@@ -105,26 +110,15 @@ struct LdsX {
   } u;
   // per-lane constants packed so that every read is one ds_read_b128 (4 LDS cycles per wave;
   // a c2 table read by pairs became ds_read2_b64 at 8 cycles, the {cal w', w'} table ds_read_b96 at 8)
-#ifndef XK_HALF
   f4v tw1[7][64];                      // {W1024^((2l) k1), W1024^((2l + 1) k1)}, k1 = 1..7
   f4v tw2[8][64];                      // {W128^(a0 s1), W128^(a0 (s1 + 1))}, s1 = 1, 3, .., 15 (a0 = l & 7)
-#else
-  c2 th1[7][64];                       // half-frame build: W512^(l k1), k1 = 1..7
-  c2 th2[7][64];                       // W64^((l & 7) s1), s1 = 1..7
-  c2 thc[8][64];                       // W1024^(l + 64 s2): the pair's radix-2 combine
-#endif
   f4v twd[8][64];                      // {W256^(q d0), W256^(q (d0 + 1))}, d0 = 1, 3, .., 15 (q = l & 15)
   f4v wdl[4][64];                      // 2chebwin of chirps (l & 15) + 16 i, i = 4 g .. 4 g + 3
   f4v wq[4][64];                       // w' = IF_scale 2blackman of samples 2 l + e + 128 i, index v = 2 i + e = 4 g .. 4 g + 3
   c2 cwq[16][64];                      // cal w' of the same samples (read by the reference-chirp wave only)
   float key[GP];                       // candidate key per group position (profile or -1)
 #ifndef XK_NOREF
-#ifndef XK_HALF
   f4v x0[512];                         // the frame's reference chirp (chirp 0) as loaded, c64 pairs (fp16: widened)
-#else
-  f4v x0[2][512];                      // half-frame build: frames 2 j' and 2 j' + 1 (put one half-step ahead)
-  c2 psum[8];                          // each wave's sum of its half of the chirp (the pair's mean)
-#endif
 #endif
 };
 
@@ -256,9 +250,6 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
   // its own, ran 0-3 % slower: the counter's line is not a hot spot at one poller per CU,
   // profiles/r06_poll_ab.txt)
   auto rdy = [&](int s_) __attribute__((always_inline)) -> unsigned* { return &ready[s_ * 32]; };
-#ifdef XK_DONE
-  unsigned* done = ready + 32 * XCD_MAX_SLOTS;
-#endif
 
   using TP = std::conditional_t<H, h4v, f4v>;
   const TP* __restrict__ iq = reinterpret_cast<const TP*>(a.iq);
@@ -266,8 +257,10 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
   // a.s16mask hold X / Nr as c32h (half the bytes).  Those blocks hold no bin that can become a
   // detection or slow-time candidate, so the slow-time rows (and the profile around a target)
   // still come from fp32 values: all-c32h slots put the slow rows at 4.5e-4 relative and the
-  // 4096-frame spectrogram at 0.15 dB against the 0.05 dB bar of SURVEY 8d.  Every group keeps
-  // the c64 stride in the slot (64 KiB; a c32h group uses its first half).
+  // 4096-frame spectrogram at 0.15 dB against the 0.05 dB bar of SURVEY 8d.  A place keeps its
+  // 256-byte row pitch in both formats (a c32h row uses the first 128 bytes): it holds a c64 chunk
+  // on one parity and possibly a c32h chunk on the other, and the wave that wrote 256 bytes where
+  // it read 128 overwrote bytes nobody reads.
   constexpr int kES = 8;
   constexpr int64_t kSlotBytes = (int64_t)NK * C * GP * kES;
   const unsigned s16m = H ? a.s16mask : 0u;
@@ -289,16 +282,11 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
     else t = x0n;
     if constexpr (!FULL)
       if (tid >= S2) t = f4v{0.f, 0.f, 0.f, 0.f};
-#ifndef XK_HALF
     (void)b;
     L.x0[tid] = t;
-#else
-    L.x0[b][tid] = t;
-#endif
   };
   if (nj > 0) ld_ref(x);
 #endif
-#ifndef XK_HALF
   for (int i = tid; i < 44 * 64; i += 512) {
     const c2 v = tov(a.xtab[i]);
     const int l = i & 63;
@@ -308,19 +296,6 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
     else { const int t = (i - XT_D1) >> 6; d = reinterpret_cast<c2*>(&L.twd[t >> 1][l]) + (t & 1); }
     *d = v;
   }
-#else
-  for (int i = XT_D1 + tid; i < XT_H1; i += 512) {
-    const int t = (i - XT_D1) >> 6;
-    reinterpret_cast<c2*>(&L.twd[t >> 1][i & 63])[t & 1] = tov(a.xtab[i]);
-  }
-  for (int i = tid; i < 22 * 64; i += 512) {
-    const c2 v = tov(a.xtab[XT_H1 + i]);
-    const int t = i >> 6, l = i & 63;
-    if (t < 7) L.th1[t][l] = v;
-    else if (t < 14) L.th2[t - 7][l] = v;
-    else L.thc[t - 14][l] = v;
-  }
-#endif
   // the Doppler window carries the two power-of-two scales of fp16 storage (exact, so the outputs
   // keep their bits): the RD map's 1 / (Nr Nd) and, for a member whose group is handed over as
   // c32h, the Nr its staging no longer multiplies back in (VALU work taken out of every step)
@@ -368,7 +343,6 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
   };
 
   c2* const rt = L.u.rt[w];                             // this wave's transpose region (range T1, T2; Doppler TD)
-#ifndef XK_HALF
   // ---------------- R: one chirp per wave (:203-205), in pieces ----------------
 #ifndef XK_NOREF
   const bool refw = k == 0 && w == 0;                   // chirp 0: the frame's reference, transformed as it is
@@ -458,163 +432,47 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
     cfence();
   };
   // R3: DFT8 over a0 and the slot stores
-  auto r_end = [&](c2 (&q0)[8], c2 (&q1)[8], char* __restrict__ slot) __attribute__((always_inline)) {
+  auto r_end = [&](c2 (&q0)[8], c2 (&q1)[8], char* __restrict__ slot, int j) __attribute__((always_inline)) {
 #ifndef XK_NORANGEFFT
     dft8p(q0);
     dft8p(q1);
 #endif
-    // bins k1 + 16 hh + 8 e + 128 s2 -> group 4 s2 + 2 e + (k1 >> 2), position lane & 31
-    const int c = k * NW + w;
+    // bins k1 + 16 hh + 8 e + 128 s2 -> group 4 s2 + 2 e + (k1 >> 2), position lane & 31: this wave's row
+    // (chirp 8 k + w) of chunk (g, k), at place xcd_place(j, g, k) of the one slot
     // slot stores are buffer stores without a cache-policy flag (the only such stores in k_rdx):
     // tools/check_vmcnt.py finds them by that to prove, on the built code, that every publish
-    // waits for them
+    // waits for them and that they wait for the wave's group loads
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(slot, (short)0, kSlotBytes, 0x00020000);
     // 16-byte stores (cdna_hip_programming.md T21: a store tail is issue-bound per instruction;
     // 4.69 -> 4.63 ms per 4096 frames against 16 8-byte stores): lane pairs swap one value, the
     // even lane stores both columns of the e = 0 row, the odd lane both of the e = 1 row
     const bool odd = lane & 1;
-    const int gl = (lane >> 5) + (odd ? 2 : 0), el = c * GP + (lane & 31) - (odd ? 1 : 0);   // group 4 s2 + gl, element el
+    const int gl = (lane >> 5) + (odd ? 2 : 0), pl = (lane & 31) - (odd ? 1 : 0);   // group 4 s2 + gl, position pl
+    // Write-after-read, wave-local: the rows stored here for frame j are the rows this wave loaded of frame
+    // j - 1 (xcd_place(j, g, k) == xcd_place(j - 1, k, g)), and nobody else reads them, so the stores only
+    // have to stay behind this wave's own group loads.  Nothing is issued between those loads and these
+    // stores, hence vmcnt(0): the loads went out a transpose and two range stages ago.
+    vm_wait<0>();
+    // place (g, k) as wave-uniform strides (xcd_place is linear in both members at either parity).  The
+    // uniform part is added into the per-lane offset, not passed as the store's scalar offset: behind a
+    // 16-byte buffer store with an SGPR offset the compiler pads no wait state before the next VALU write of
+    // the store's data registers, and on gfx950 the store then read the next s2's values in the last lanes of
+    // each 16-lane group (stale-looking 32-byte pieces in the slot, some launches only).
+    const int sg = xcd_place(j, 1, 0) * XCD_PLACE_BYTES, sk = xcd_place(j, 0, 1) * XCD_PLACE_BYTES;
+    const int vb = gl * sg + k * sk + w * XCD_ROW_BYTES;
 #pragma unroll
     for (int s2 = 0; s2 < 8; ++s2) {
       const f4v v = pair_cols(q0[s2], q1[s2], odd);
-      const int gb = (4 * s2 + gl) * C * GP * 8;
-      if (H && ((s16m >> s2) & 1)) {   // c32h block (wave-uniform): X / Nr, 8 bytes per lane
+      if (H && ((s16m >> s2) & 1)) {   // c32h block (wave-uniform): X / Nr, 8 bytes per lane, the row's first half
         const __half2 h0 = __floats2half2_rn(v.x * kXS, v.y * kXS), h1 = __floats2half2_rn(v.z * kXS, v.w * kXS);
         __builtin_amdgcn_raw_buffer_store_b64(u2v{__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1)}, rs,
-                                              gb + el * 4, 0, 0);
+                                              vb + pl * 4 + 4 * s2 * sg, 0, 0);
       } else {
-        __builtin_amdgcn_raw_buffer_store_b128(v, rs, gb + el * 8, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(v, rs, vb + pl * 8 + 4 * s2 * sg, 0, 0);
       }
     }
   };
 
-#else
-  // ---------------- R, half-frame build (-DXK_HALF): a wave pair per chirp (:203-205) ----------------
-  // Half-step h holds half hf = h & 1 of frame h >> 1: member k's waves w and w + 4 share chirp
-  // 128 hf + 4 k + (w & 3), wave w taking the samples of parity e = w >> 2 (n = 2 m + e, m = lane + 64 i).
-  // Each wave runs a 512-point FFT of its samples (DFT8 over i, twiddle W512^(lane k1), LDS transpose,
-  // DFT8 over l1, twiddle W64^(l0 s1), LDS transpose, DFT8 over l0: F[r'] in lane 8 s1 + k1, register s2,
-  // r' = lane + 64 s2), and the pair combines them (radix 2 in time): X[r'] = E[r'] + W1024^r' O[r'] in
-  // wave e = 0, X[r' + 512] = E[r'] - W1024^r' O[r'] in wave e = 1, through LDS after a barrier.  Group g
-  // of the half slot then holds bins 32 g .. 32 g + 31 (xcd_bin of the half build).  Both waves read the
-  // whole chirp (16-byte sample pairs) so that each forms the :204 mean over all 1024 samples itself.
-#ifdef XK_NOREF
-#error "the half-frame build keeps the reference chirp"
-#endif
-  const int eh = w >> 2;                                // this wave's sample parity (wave-uniform)
-  const bool refw0 = k == 0 && (w & 3) == 0;            // chirp 0 (half 0) is the frame's reference
-  // this wave's 512 samples of the chirp (8-byte loads; c32h: 4-byte)
-  typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-  using XH = std::conditional_t<H, h2v, c2>;
-  auto ld_chirp_h = [&](int64_t f, int hf, XH (&xin)[8]) __attribute__((always_inline)) {
-    const XH* __restrict__ q = reinterpret_cast<const XH*>(iq + (f * C + (128 * hf + 4 * k + (w & 3))) * (int64_t)S2) + eh;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int p = lane + 64 * i;
-      if constexpr (FULL) xin[i] = __builtin_nontemporal_load(q + 2 * p);
-      else xin[i] = __builtin_nontemporal_load(q + 2 * (p < S2 ? p : 0));
-    }
-  };
-  // before B2: d = x - x_0 (x for the reference chirp) of this wave's samples, its sum to LDS for the
-  // partner (the :204 mean is over all 1024 samples); x_0 of frame j' sits in buffer j' & 1 from half-step 2 j' - 1
-  auto rh_sum = [&](const XH (&xin)[8], bool refw, int xb, c2 (&d)[8]) __attribute__((always_inline)) {
-    const float dsc = refw ? 0.f : 1.f;
-    const c2* x0p = reinterpret_cast<const c2*>(L.x0[xb]) + eh;
-    c2 sm{0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      c2 t;
-      if constexpr (H) t = __builtin_convertvector(xin[i], c2);
-      else t = xin[i];
-      t = __builtin_elementwise_fma(c2{-dsc, -dsc}, x0p[2 * (lane + 64 * i)], t);
-      if constexpr (!FULL)
-        if (!(lane + 64 * i < S2)) t = c2{0.f, 0.f};
-      d[i] = t;
-      sm += t;
-    }
-    sm = wave_sum_c(sm);
-    if (lane == 0) L.psum[w] = sm;
-  };
-  // R1 (after B2): the mean, (d - mu) w' (the reference chirp: (x - cal - mu) w'), DFT8 over i, twiddle W512^(lane k1)
-  auto rh_prep = [&](c2 (&z)[8], bool refw) __attribute__((always_inline)) {
-    const c2 csum_w = refw ? csum : c2{0.f, 0.f};
-    const c2 mu = (L.psum[w] + L.psum[w ^ 4] - csum_w) * invS;   // a + b == b + a: the pair's mu agree
-    float wv[8];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const f4v t = L.wq[g][lane];                      // w' of samples 2 lane + e + 128 i, v = 2 i + e = 4 g ..
-      wv[2 * g] = eh ? t.y : t.x;
-      wv[2 * g + 1] = eh ? t.w : t.z;
-    }
-    if (refw) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) z[i] = __builtin_elementwise_fma(z[i] - mu, c2{wv[i], wv[i]}, -L.cwq[2 * i + eh][lane]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) z[i] = (z[i] - mu) * wv[i];
-    }
-    dft8p(z);
-#pragma unroll
-    for (int k1 = 1; k1 < 8; ++k1) z[k1] = cmul_a(z[k1], L.th1[k1 - 1][lane]);
-  };
-  // T1 (lane l, register k1 -> lane 8 k1 + l0, register l1; row stride 72: conflict-free both ways)
-  auto rh_t1w = [&](const c2 (&z)[8]) __attribute__((always_inline)) {
-#pragma unroll
-    for (int k1 = 0; k1 < 8; ++k1) rt[k1 * 72 + lane] = z[k1];
-    cfence();
-  };
-  auto rh_t1r = [&](c2 (&u)[8]) __attribute__((always_inline)) {
-#pragma unroll
-    for (int l1 = 0; l1 < 8; ++l1) u[l1] = rt[(lane >> 3) * 72 + (lane & 7) + 8 * l1];
-    cfence();
-  };
-  // R2: DFT8 over l1, twiddle W64^(l0 s1); T2 (lane 8 k1 + l0, register s1 -> lane 8 s1 + k1, register l0;
-  // element s1 97 + 8 k1 + 4 (k1 >> 2) + l0: conflict-free both ways); R3: DFT8 over l0
-  auto rh_mid = [&](c2 (&u)[8], c2 (&v)[8]) __attribute__((always_inline)) {
-    dft8p(u);
-#pragma unroll
-    for (int s1 = 1; s1 < 8; ++s1) u[s1] = cmul_a(u[s1], L.th2[s1 - 1][lane]);
-#pragma unroll
-    for (int s1 = 0; s1 < 8; ++s1) rt[s1 * 97 + lane + 4 * (lane >> 5)] = u[s1];
-    cfence();
-    const int rb = (lane >> 3) * 97 + 8 * (lane & 7) + 4 * ((lane & 7) >> 2);
-#pragma unroll
-    for (int l0 = 0; l0 < 8; ++l0) v[l0] = rt[rb + l0];
-    cfence();
-    dft8p(v);
-#pragma unroll
-    for (int s2 = 0; s2 < 8; ++s2) rt[s2 * 64 + lane] = v[s2];   // for the partner wave, read after B4
-  };
-  // after B4: the combine and the slot stores (bins 512 e + lane + 64 s2 -> group 16 e + 2 s2 + (lane >> 5),
-  // position lane & 31; the 16-byte stores pair registers 2 t, 2 t + 1 as the frame build pairs e = 0, 1)
-  auto rh_end = [&](c2 (&v)[8], char* __restrict__ slot) __attribute__((always_inline)) {
-    const c2* pr = L.u.rt[w ^ 4];
-    if (eh) {
-#pragma unroll
-      for (int s2 = 0; s2 < 8; ++s2) v[s2] = pr[s2 * 64 + lane] - cmul_a(v[s2], L.thc[s2][lane]);
-    } else {
-#pragma unroll
-      for (int s2 = 0; s2 < 8; ++s2) v[s2] = v[s2] + cmul_a(pr[s2 * 64 + lane], L.thc[s2][lane]);
-    }
-    constexpr int64_t kHalfBytes = (int64_t)NK * (C / 2) * GP * kES;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(slot, (short)0, kHalfBytes, 0x00020000);
-    const bool odd = lane & 1;
-    const int ch = 4 * k + (w & 3);
-    const int gl = (lane >> 5) + (odd ? 2 : 0), el = ch * GP + (lane & 31) - (odd ? 1 : 0);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const f4v pv = pair_cols(v[2 * t], v[2 * t + 1], odd);
-      const int gb = (16 * eh + 4 * t + gl) * (C / 2) * GP * 8;
-      if (H && ((s16m >> (4 * eh + t)) & 1)) {   // c32h block (wave-uniform): X / Nr
-        const __half2 h0 = __floats2half2_rn(pv.x * kXS, pv.y * kXS), h1 = __floats2half2_rn(pv.z * kXS, pv.w * kXS);
-        __builtin_amdgcn_raw_buffer_store_b64(u2v{__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1)}, rs,
-                                              gb + el * 4, 0, 0);
-      } else {
-        __builtin_amdgcn_raw_buffer_store_b128(pv, rs, gb + el * 8, 0, 0);
-      }
-    }
-  };
-#endif
 
   // ---------------- D: the 32 bins of group k (:210, :216-219, :257-259), in pieces ----------------
   // buffer_load ... sc1: the CU's L1 is bypassed (no stale lines from the slot's
@@ -623,19 +481,28 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
   // into the same fp32 staging image)
   // G16 (compile time: the step loop is instantiated per member format): a c32h group is 32 KiB,
   // 4 loads per thread, widened and scaled back by Nr into the same fp32 staging image
-  auto ld_group = [&](const char* __restrict__ grp, f4v (&t)[8], auto G16) __attribute__((always_inline)) {
-    constexpr int NL = decltype(G16)::value ? 4 : 8;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(grp), (short)0, C * GP * kES, 0x00020000);
+  // Wave w loads row w of the 32 chunks (k, m) of frame j: chirps 8 m + w of group k, 256-byte rows (c32h:
+  // 128) at places xcd_place(j, k, m).  These are the rows its R3 then overwrites (r_end).
+  auto ld_group = [&](const char* __restrict__ slot, int j, f4v (&t)[8], auto G16) __attribute__((always_inline)) {
+    constexpr bool g16_ = decltype(G16)::value;
+    constexpr int NL = g16_ ? 4 : 8;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(slot), (short)0, kSlotBytes, 0x00020000);
+    // place (k, m) as wave-uniform strides, as in r_end: one per-lane offset, the rest scalar
+    const int sk = xcd_place(j, 1, 0) * XCD_PLACE_BYTES, sm = xcd_place(j, 0, 1) * XCD_PLACE_BYTES;
+    const int vo = g16_ ? (lane >> 3) * sm + (lane & 7) * 16 : (lane >> 4) * sm + (lane & 15) * 16;
+    const int sb = k * sk + w * XCD_ROW_BYTES;
 #pragma unroll
-    for (int i = 0; i < NL; ++i) t[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, (tid + 512 * i) * 16, 0, 16);
+    for (int i = 0; i < NL; ++i) t[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, sb + (g16_ ? 8 : 4) * i * sm, 16);
   };
+  // the same [chirp][34] image whichever wave holds a chirp.  ds_write_b128 is served in groups of 8
+  // contiguous lanes: they write 8 consecutive 16-byte pieces of one chirp's row, 8 different bank groups.
   auto stage = [&](const f4v (&t)[8], auto G16) __attribute__((always_inline)) {
     if constexpr (decltype(G16)::value) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int e = tid + 512 * i;            // 16-byte piece: chirp e >> 3, positions 4 (e & 7) .. + 3
+        const int e = lane & 7;                 // 16-byte piece: chirp 8 m + w, positions 4 e .. + 3
         const u4v u = __builtin_bit_cast(u4v, t[i]);
-        f4v* d = &L.u.stg[(e >> 3) * 17 + (e & 7) * 2];
+        f4v* d = &L.u.stg[(8 * (8 * i + (lane >> 3)) + w) * 17 + e * 2];
         // kept as X / Nr: the rows below scale their outputs, the Doppler window the rest
         // lanes 4-7 of each 8-lane store group write their upper half first: the group's 8 stores
         // then hit 8 different 16-byte bank groups (conflict-free ds_write_b128)
@@ -655,10 +522,7 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
       }
     } else {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int e4 = tid + 512 * i;
-        L.u.stg[(e4 >> 4) * 17 + (e4 & 15)] = t[i];
-      }
+      for (int i = 0; i < 8; ++i) L.u.stg[(8 * (4 * i + (lane >> 4)) + w) * 17 + (lane & 15)] = t[i];
     }
   };
   const int pp = lane >> 4, q = lane & 15, p = 4 * w + pp;
@@ -800,25 +664,11 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
     }
   };
 
-  char* __restrict__ slots0 = reinterpret_cast<char*>(a.xcube) + (int64_t)x * NS * kSlotBytes;
-#ifdef XK_DONE       // A/B: one slot per XCD, its reuse proven by a done counter (tools/r04_probe.hip part J)
-  auto slot = [&](int) __attribute__((always_inline)) { return slots0; };
-#else
-  auto slot = [&](int j) __attribute__((always_inline)) { return slots0 + (int64_t)(j % kNS) * kSlotBytes; };
-#endif
+  char* __restrict__ slot = reinterpret_cast<char*>(a.xcube) + (int64_t)x * NS * kSlotBytes;   // the XCD's one slot
   auto frame = [&](int j) __attribute__((always_inline)) { return x + (int64_t)T * j; };
-#ifndef XK_HALF
   TP xin[8];
-#else
-  XH xin[8];
-#endif
   f4v grp[8];
-#ifndef XK_HALF
   if (nj > 0) ld_chirp(frame(0), xin);
-#else
-  if (nj > 0) ld_chirp_h(frame(0), 0, xin);
-#endif
-#ifndef XK_HALF
   // Step j runs R(j) and D(j - 2) side by side in every wave, so that the range FFT's and the
   // Doppler FFT's dependency chains (DPP sums, LDS transposes) cover each other:
   //   B1 (frame j's reference chirp into LDS) -> staging of group j - 2 (loaded into registers
@@ -826,15 +676,17 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
   //   profile, keys -> B3 -> candidates -> R1 | D3 -> the next frame's chirp loads (R1 freed the registers)
   //   -> wave 0 polls ready(j - 1), every wave loads group k of frame j - 1 -> TD -> T1 | D DFT16
   //   -> R2 -> T2 -> R3 + slot stores -> RD stores.
-  // The group of frame j - 1 is read about one step after its slot was written, while the
-  // slot's lines are still in the XCD's L2 (a ring of kNS slots: 4 MiB at kNS = 2).
-  // Slot reuse needs no done counters: R(j) writes its slot after this member saw ready(j - 1),
-  // i.e. after every member published R(j - 1); a member publishes R(j - 1) only after its slot
-  // stores of R(j - 1) returned, and its group loads of frame j - 2 were issued before them
-  // (vmcnt retires in order), so every read of frames <= j - 2 is done: kNS >= 2 suffices.
+  // The group of frame j - 1 is read about one step after it was written, while the slot's lines
+  // are still in the XCD's L2 (one slot: 2 MiB).
+  // Rewriting the one slot needs no done counters and no second slot.  R(j)'s stores of this wave go
+  // to the rows the wave loaded of frame j - 1 (xcd_place(j, g, k) == xcd_place(j - 1, k, g)), which no
+  // other wave reads: they wait for the wave's own group loads (r_end) and for nothing else.  The
+  // rows other members read of frame j - 1 are not touched by this member at all.  A place goes
+  // back and forth between two members: g writes chunk (k, g) of frame j - 1, k reads it (after
+  // ready(j - 1)) and writes chunk (g, k) of frame j over it, g reads that (after ready(j)) and so on.
   // The publish wait counts what every path issues after the slot stores: D(j - 3)'s RD stores
-  // (or row peaks); tools/check_vmcnt.py proves it on the built code.  With FULL and three frames or more on the XCD, steps 0-2 and the last two are
-  // peeled, every flag a compile-time constant; every other launch takes the one copy with run-time flags (below).
+  // (or row peaks); tools/check_vmcnt.py proves both waits on the built code.  With FULL and three frames or
+  // more on the XCD, steps 0-2 and the last two are peeled, every flag a compile-time constant; every other launch takes the one copy with run-time flags (below).
   constexpr int kRDs = RD ? 16 : 1;                             // D's stores after the slot stores (RD rows / row peak)
   // flags: std::integral_constant (folded: straight-line copies) or bool (the short-launch copy)
   auto body = [&](int j, auto DJ, auto RJ, auto PUB, auto CNT, auto GJ, auto NEXT, auto G16) __attribute__((always_inline)) {
@@ -916,7 +768,7 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
       } else {
         while (*reinterpret_cast<volatile unsigned*>(&gflag) < (unsigned)j) __builtin_amdgcn_s_sleep(1);
       }
-      ld_group(slot(j - kLag) + (int64_t)k * C * GP * kES, grp, G16);
+      ld_group(slot, j - kLag, grp, G16);
     }
     stamp(7);
 #ifndef XK_NODOPFFT
@@ -940,21 +792,7 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
       c2 q0[8], q1[8];
       r_mid(u);
       r_t2(u, q0, q1);
-#ifdef XK_DONE
-      static_assert(kLag == 1, "the done-counter A/B is written for lag 1");
-      // one slot: every member's group loads of frame j - 1 (issued above) must have returned
-      // before R(j) rewrites it.  Count them out (done), then wait for the whole team.
-      if (gj) {
-        vm_wait<0>();
-        __syncthreads();
-        if (w == 0) {
-          if (lane == 0) __hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          wait_ge(done, (unsigned)(NK * j), a.xctr + XCD_ABORT, a.xerr);
-        }
-        __syncthreads();
-      }
-#endif
-      r_end(q0, q1, slot(j));
+      r_end(q0, q1, slot, j);
     }
     stamp(8);
     if (dj) d_store(fd, xv);           // after R(j)'s slot stores (RD stores before them: 4.64 vs 4.36 ms)
@@ -967,24 +805,6 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
   using C1 = std::integral_constant<int, 0>;
   using CF = std::integral_constant<int, kRDs>;
   auto run = [&](auto G16) __attribute__((always_inline)) {
-#if XK_LAG == 2
-    // lag 2: the Doppler runs three steps behind; 4 slots
-    if (nj >= 5) {
-      //   j       DJ   RJ   PUB  CNT                              GJ   NEXT
-      body(0,      F_{}, T_{}, F_{}, C0{},                          F_{}, T_{}, G16);
-      body(1,      F_{}, T_{}, T_{}, C0{},                          F_{}, T_{}, G16);
-      body(2,      F_{}, T_{}, T_{}, C0{},                          T_{}, T_{}, G16);
-      body(3,      T_{}, T_{}, T_{}, C0{},                          T_{}, T_{}, G16);
-      for (int j = 4; j < nj; ++j) body(j, T_{}, T_{}, T_{}, CF{}, T_{}, T_{}, G16);
-      body(nj,     T_{}, F_{}, T_{}, CF{},                          T_{}, F_{}, G16);
-      body(nj + 1, T_{}, F_{}, F_{}, C0{},                          T_{}, F_{}, G16);
-      body(nj + 2, T_{}, F_{}, F_{}, C0{},                          F_{}, F_{}, G16);
-    } else {
-      for (int j = 0; j < nj + 3; ++j)
-        body(j, j >= 3, j < nj, j >= 1 && j - 1 < nj, C0{}, j >= 2 && j - 2 < nj, j + 1 < nj, G16);
-    }
-    return;
-#endif
     // nts < Nr (FULL false) takes the run-time copy whatever nj is.  Its peeled copies and its run-time copy
     // did not round alike (measured; most likely a multiply and an add contracted in one copy and not in the
     // other, the compiler's choice per inlined copy), so a frame's last bits depended on how many frames its
@@ -1012,168 +832,6 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
   } else {
     run(F_{});
   }
-#else
-  // Half-frame build (-DXK_HALF): the hand-off unit is half a frame (128 chirps, a 1 MiB half slot), so the
-  // team runs two half-steps per frame.  Half-step h: B1 -> (h even) frame h / 2's reference chirp into LDS
-  // -> (D1) staging of group k of frame jd (its two halves loaded in the two half-steps before) -> B2 ->
-  // publish R(h - 1) -> (D1) rows, profile, keys -> B3 -> candidates -> R1 -> the next half-step's chirp
-  // loads -> wave 0's early poll of ready(h - lag) -> (D1) D3 -> every wave loads its half of group k of
-  // R(h - lag) -> (D2) TD -> T1 | (D2) DFT16 -> R2, T2, R3 -> B4 (the pair's halves in LDS) -> combine,
-  // slot stores -> (D2) RD stores.  D1 of frame jd runs in half-step 2 jd + 2 + lag, D2 in the next one,
-  // so the Doppler ends two frames behind the range FFT, as in the frame build.  Slot reuse: R(h) rewrites
-  // half slot h mod kNS after this member saw ready(h - lag); the members' loads of R(h - 2 lag) were issued
-  // before their slot stores of R(h - lag), so kNS = 2 lag half slots suffice (the frame build's argument).
-  (void)ld_chirp;                                              // the frame build's pieces, unused here
-  (void)ld_group;
-  (void)slot;
-  (void)stamp;
-  constexpr int64_t kHalfSlot = (int64_t)NK * (C / 2) * GP * kES;
-  auto hslot = [&](int h) __attribute__((always_inline)) { return slots0 + (int64_t)(h % kNS) * kHalfSlot; };
-  constexpr int kRDs = RD ? 16 : 1;
-  const int nh = 2 * nj;                                        // half-steps with range work
-  c2 xvd[16];                                                   // D(jd)'s rows, from D1 to D2
-  // load this member's half of group k of R(hh) into grp[hf * NL ..] (NL = 4 c64 / 2 c32h pieces per thread)
-  auto ld_group_h = [&](int hh, auto HFL, auto G16) __attribute__((always_inline)) {
-    constexpr int NL = decltype(G16)::value ? 2 : 4;
-    const char* grb = hslot(hh) + (int64_t)k * (C / 2) * GP * kES;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(grb), (short)0, (C / 2) * GP * kES, 0x00020000);
-    if constexpr (std::is_same_v<decltype(HFL), bool>) {
-      // value selects, not two stores: a store through a selected address would keep grp in scratch
-#pragma unroll
-      for (int i = 0; i < NL; ++i) {
-        const f4v t = __builtin_amdgcn_raw_buffer_load_b128(rs, (tid + 512 * i) * 16, 0, 16);
-        grp[i] = HFL ? grp[i] : t;
-        grp[NL + i] = HFL ? t : grp[NL + i];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < NL; ++i)
-        grp[decltype(HFL)::value * NL + i] = __builtin_amdgcn_raw_buffer_load_b128(rs, (tid + 512 * i) * 16, 0, 16);
-    }
-  };
-  // gflag through an LDS pointer: the flat accesses of the frame build trip LLVM 20's aperture-compare
-  // bug in the half-step copies
-  typedef __attribute__((address_space(3))) unsigned lu32;
-  lu32* const gfl = (lu32*)&gflag;
-#define XK_HPOLL()                                                                                                  \
-  do {                                                                                                              \
-    wait_ge(rdy((h - kLag) % kNS), (unsigned)(NK * ((h - kLag) / kNS + 1)), a.xctr + XCD_ABORT, a.xerr);   \
-    if (lane == 0) __hip_atomic_store(gfl, (unsigned)h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);             \
-  } while (0)
-  // flags: std::integral_constant in the steady pairs (every wait count static), bool elsewhere
-  auto hbody = [&](int h, auto D1, auto D2, auto RJ, auto PUB, auto CNT, auto GJ, auto NEXT, auto HF, auto GHF,
-                   auto G16) __attribute__((always_inline)) {
-    const bool d1 = D1, d2 = D2, rj = RJ, pub = PUB, gj = GJ, next = NEXT;
-    const bool hf = HF;
-    const int64_t fd1 = frame((h - 2 - kLag) >> 1), fd2 = frame((h - 3 - kLag) >> 1);
-    if (h >= 1) __syncthreads();       // B1
-    if (hf && h + 1 < nh) put_ref(((h + 1) >> 1) & 1);   // frame (h + 1) / 2's reference chirp, read from half-step h + 1
-    if (d1) stage(grp, G16);
-    c2 z[8], u[8];
-    if (rj) rh_sum(xin, refw0 && !hf, (h >> 1) & 1, z);
-    if constexpr (std::is_same_v<decltype(PUB), bool>) vm_wait<0>();
-    else if (pub) vm_wait<decltype(CNT)::value>();
-    __syncthreads();                   // B2
-    if (pub)
-      if (lane == 0)
-        __hip_atomic_fetch_add(w == 0 ? rdy((h - 1) % kNS) : a.xctr + XCD_IDLE + (x * NK + k) * 32 + w,
-                               w == 0 ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    c2 x0r{0.f, 0.f}, dmu{0.f, 0.f};
-    if (d1) d_rows(fd1, xvd, x0r, dmu, G16);
-    if (d1) __syncthreads();           // B3
-    if (d1) d_cand(fd1, xvd, x0r, G16);
-    if (rj) rh_prep(z, refw0 && !hf);
-    if (next) {
-      const int hn = h + 1;
-      if (!hf && h + 2 < nh) ld_ref(frame((h >> 1) + 1));   // put at B1 of half-step h + 1
-      ld_chirp_h(frame(hn >> 1), hn & 1, xin);
-    }
-    if (XK_POLLAT == 2 && gj && w == 0) XK_HPOLL();
-    if (d1) d_a(xvd, dmu);
-    if (gj) {
-      if (w == 0) {
-        XK_HPOLL();
-      } else {
-        while (__hip_atomic_load(gfl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < (unsigned)h) __builtin_amdgcn_s_sleep(1);
-      }
-      ld_group_h(h - kLag, GHF, G16);
-    }
-    if (d2) d_td(xvd);
-    if (rj) rh_t1w(z);
-    if (d2) dft16p<1>(xvd);
-    if (rj) {
-      rh_t1r(u);
-      rh_mid(u, z);
-    }
-    __syncthreads();                   // B4: both halves of every pair's chirp in LDS
-    if (rj) rh_end(z, hslot(h));
-    if (d2) d_store(fd2, xvd);
-  };
-#undef XK_HPOLL
-  using T_ = std::true_type;
-  using F_ = std::false_type;
-  using C0 = std::integral_constant<int, 0>;
-  // Peeled: the first P0 half-steps and the last 4 + lag, every flag and wait count a compile-time constant
-  // (tools/check_vmcnt.py's proof is path-insensitive); the steady pairs in between; a short launch runs
-  // one copy with run-time flags, every publish waiting for everything.
-  constexpr int P0 = kLag == 1 ? 4 : 6;
-  const int nhs = nh + 2 + kLag;                               // half-steps in all
-  auto pro = [&](auto HC, auto G16) __attribute__((always_inline)) {
-    constexpr int h = decltype(HC)::value;
-    hbody(h, std::bool_constant<(h >= 2 + kLag && ((h - 2 - kLag) & 1) == 0)>{},
-          std::bool_constant<(h >= 3 + kLag && ((h - 3 - kLag) & 1) == 0)>{}, T_{}, std::bool_constant<(h >= 1)>{},
-          std::integral_constant<int, (h - 1 >= 3 + kLag && ((h - 4 - kLag) & 1) == 0) ? kRDs : 0>{},
-          std::bool_constant<(h >= kLag)>{}, T_{}, std::bool_constant<(h & 1) != 0>{},
-          std::bool_constant<(((h - kLag) & 1) != 0)>{}, G16);
-  };
-  auto mid = [&](int h, auto G16) __attribute__((always_inline)) {   // h even, both half-steps steady
-    constexpr bool d1o = kLag & 1;                              // D1 on odd half-steps at lag 1, even ones at lag 2
-    hbody(h, std::bool_constant<!d1o>{}, std::bool_constant<d1o>{}, T_{}, T_{},
-          std::integral_constant<int, d1o ? 0 : kRDs>{}, T_{}, T_{}, F_{}, std::bool_constant<(kLag & 1) != 0>{}, G16);
-    hbody(h + 1, std::bool_constant<d1o>{}, std::bool_constant<!d1o>{}, T_{}, T_{},
-          std::integral_constant<int, d1o ? kRDs : 0>{}, T_{}, T_{}, T_{}, std::bool_constant<(kLag & 1) == 0>{}, G16);
-  };
-  auto epi = [&](auto IC, auto G16) __attribute__((always_inline)) {   // half-step nh - 2 + i (nh even)
-    constexpr int i = decltype(IC)::value;
-    hbody(nh - 2 + i, std::bool_constant<((kLag + i) & 1) == 0 && i < 4 + kLag>{},
-          std::bool_constant<((kLag + i + 1) & 1) == 0 && i < 5 + kLag>{}, std::bool_constant<(i < 2)>{},
-          std::bool_constant<(i < 3)>{}, std::integral_constant<int, ((kLag + i) & 1) == 0 ? kRDs : 0>{},
-          std::bool_constant<(i < 2 + kLag)>{}, std::bool_constant<(i == 0)>{}, std::bool_constant<(i & 1) != 0>{},
-          std::bool_constant<((i + kLag) & 1) != 0>{}, G16);
-  };
-  auto hrun = [&](auto G16) __attribute__((always_inline)) {
-    if (nh - 2 > P0) {
-      using std::integral_constant;
-      pro(integral_constant<int, 0>{}, G16);
-      pro(integral_constant<int, 1>{}, G16);
-      pro(integral_constant<int, 2>{}, G16);
-      pro(integral_constant<int, 3>{}, G16);
-      if constexpr (P0 > 4) {
-        pro(integral_constant<int, 4>{}, G16);
-        pro(integral_constant<int, 5>{}, G16);
-      }
-      for (int h = P0; h < nh - 2; h += 2) mid(h, G16);
-      epi(integral_constant<int, 0>{}, G16);
-      epi(integral_constant<int, 1>{}, G16);
-      epi(integral_constant<int, 2>{}, G16);
-      epi(integral_constant<int, 3>{}, G16);
-      epi(integral_constant<int, 4>{}, G16);
-      if constexpr (kLag == 2) epi(integral_constant<int, 5>{}, G16);
-    } else {
-      for (int h = 0; h < nhs; ++h) {
-        const int h1 = h - 2 - kLag, h2 = h - 3 - kLag;
-        hbody(h, h1 >= 0 && !(h1 & 1) && (h1 >> 1) < nj, h2 >= 0 && !(h2 & 1) && (h2 >> 1) < nj, h < nh,
-              h >= 1 && h - 1 < nh, C0{}, h >= kLag && h - kLag < nh, h + 1 < nh, (h & 1) != 0, ((h - kLag) & 1) != 0, G16);
-      }
-    }
-  };
-  if constexpr (H) {
-    if (g16) hrun(T_{});
-    else hrun(F_{});
-  } else {
-    hrun(F_{});
-  }
-#endif
   if (stamper) {
     a.clk[2] = __builtin_amdgcn_s_memtime();
     a.clk[3] = __builtin_amdgcn_s_memrealtime();
@@ -1214,7 +872,7 @@ hipEvent_t xcd_chain_ev[64] = {};
 
 hipError_t launch_xcd(const OnePassArgs& a, hipStream_t s) {
   if (a.F <= 0) return hipSuccess;
-  if (!onepass_supported(a.S, a.C, op::NR, a.C) || a.slots < 4 || a.slots > XCD_MAX_SLOTS) return hipErrorInvalidValue;
+  if (!onepass_supported(a.S, a.C, op::NR, a.C) || a.slots < 1 || a.slots > XCD_MAX_SLOTS) return hipErrorInvalidValue;
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;

@@ -24,6 +24,20 @@ fails the check.  Exit status 1 on any uncovered path:
 the Makefile then fails the build, so a compiler change that splits, merges or
 reorders a store cannot silently publish a slot before its bytes are in L2.
 
+Second obligation (the in-place slot).  k_rdx keeps one slot per XCD and rewrites it every
+frame: the rows a wave stores for frame j + 1 are the rows it loaded (``buffer_load_* ... sc1``,
+the group loads; k_rdx issues no other sc1 loads) of frame j, and no other wave reads them
+(xcd_place, fmcw_internal.h).  The write-after-read hazard is therefore wave-local, and is covered
+when, on every control-flow path into every slot store, the wave's preceding group loads have
+returned: some ``s_waitcnt vmcnt(N)`` between the last group load and the store with at least N
+vector-memory operations issued between that load and the wait (the same in-order argument; the
+earlier group loads then returned too).  No barrier is involved, so every wait on the way counts.
+A path that reaches the kernel's entry without a group load (the first step) is fine.
+A slot store of more than 8 bytes must also keep a constant scalar offset: behind a
+``buffer_store_dwordx3/x4`` whose soffset is an SGPR the compiler pads no wait state before the
+next VALU write of the store's data registers, and on gfx950 such a store picked up the next
+store's values in some lanes (kernels_xcd.hip, r_end).
+
   python tools/check_vmcnt.py kernels_xcd.s [--quiet]
 """
 from __future__ import annotations
@@ -92,6 +106,19 @@ def is_slot_store(ins: str) -> bool:
 def is_vmem(ins: str) -> bool:
     op = ins.split()[0]
     return op.startswith(("global_", "buffer_", "scratch_", "flat_")) and op not in ("buffer_inv",)
+
+
+def wide_store_sgpr_offset(ins: str) -> bool:
+    """A slot store of 12 or 16 bytes per lane whose scalar offset is a register."""
+    if not is_slot_store(ins) or not ins.split()[0].endswith(("x3", "x4")):
+        return False
+    ops = [o.strip() for o in ins.split(None, 1)[1].split(",")]
+    soff = ops[-1].split()[0] if ops else ""
+    return soff.startswith(("s", "m0", "ttmp")) and not soff.startswith("s[")
+
+
+def is_group_load(ins: str) -> bool:
+    return ins.startswith("buffer_load") and "sc1" in ins.split()[1:]
 
 
 RE_RELAX = re.compile(r"^s_add_u32\s+(s\d+),\s*\1,\s*\((\.LBB\d+_\d+)-\.Lpost_getpc\d+\)")
@@ -190,6 +217,57 @@ def check_function(name, lines, quiet=False):
     return not bad and (stores == 0 or pubs)
 
 
+def check_inplace(name, lines, quiet=False):
+    """Every slot store waits for the wave's preceding sc1 group loads (module docstring)."""
+    bl = blocks(lines)
+    pred = cfg(bl)
+    stores = [(b, k) for b, (_, ins) in enumerate(bl) for k, s in enumerate(ins) if is_slot_store(s)]
+    if any(ins and ins[-1].startswith("s_setpc_b64") and relaxed_target(ins) is None for _, ins in bl):
+        if not quiet:
+            print(f"{name}: s_setpc_b64 with no s_getpc/s_add_u32 target: the CFG is not followed, FAIL")
+        return False
+    bad = []
+    loads = 0
+    sgpr = [(bl[b][0], bl[b][1][k]) for b, k in stores if wide_store_sgpr_offset(bl[b][1][k])]
+    for lab, ins in sgpr[:5]:
+        print(f"  slot store in {lab} with an SGPR offset (no wait state before its data registers are rewritten): {ins}")
+    for b0, k0 in stores:
+        # backward search; state = the smallest "still needed" count over the waits passed
+        best = {}
+        work = [(b0, k0, INF, ())]
+        while work:
+            b, k, rem, path = work.pop()
+            ins = bl[b][1]
+            hit = False
+            for i in range(k - 1, -1, -1):
+                s = ins[i]
+                m = RE_VMCNT.search(s) if s.startswith("s_waitcnt") else None
+                if m:
+                    rem = min(rem, int(m.group(1)))
+                if is_group_load(s):
+                    loads += 1
+                    if rem > 0:
+                        bad.append((bl[b0][0], bl[b][0], rem, path + (bl[b][0],)))
+                    hit = True
+                    break
+                if is_vmem(s) and rem != INF:
+                    rem -= 1
+            if hit:
+                continue
+            for p in pred[b]:
+                if p in best and best[p] >= rem:
+                    continue
+                best[p] = rem
+                work.append((p, len(bl[p][1]), rem, (path + (bl[b][0],))[-6:]))
+    if not quiet:
+        print(f"{name}: {len(stores)} slot stores behind their group loads on every path "
+              f"({loads} load-to-store paths), {'OK' if not bad and not sgpr else str(len(bad)) + ' uncovered path(s), ' + str(len(sgpr)) + ' SGPR-offset store(s)'}")
+    for st, blk, rem, path in bad[:5]:
+        need = "no wait on the way" if rem == INF else f"needs {int(rem)} more ops"
+        print(f"  slot store in {st}: group load in {blk} not waited for ({need}); path ...{' <- '.join(path)}")
+    return not bad and not sgpr
+
+
 def main(argv):
     quiet = "--quiet" in argv
     paths = [a for a in argv if not a.startswith("--")]
@@ -200,6 +278,7 @@ def main(argv):
         n += len(fns)
         for name, lines in fns.items():
             ok &= bool(check_function(name, lines, quiet))
+            ok &= bool(check_inplace(name, lines, quiet))
     if n == 0:
         print("check_vmcnt: no k_rdx function found", file=sys.stderr)
         return 1
