@@ -650,17 +650,27 @@ __global__ __launch_bounds__(512, 1) void k_rdx(OnePassArgs a) {
           __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, xv[(d1s + 8) & 15]), rr, off * 8, 0, kRdAux);
         }
       }
-    } else {   // :233 [val, di] = max(abs(.)) of the row: exact max of |D|^2, then its first position
+    } else {   // :233 [val, di] = max(abs(.)) of the row: exact max of |D|^2, then the first position of its magnitude
       float m = abs2v(xv[8]);
 #pragma unroll
       for (int d1s = 1; d1s < 16; ++d1s) m = fmaxf(m, abs2v(xv[(d1s + 8) & 15]));
       const float rm = __int_as_float(row_max16(__float_as_int(m)));
+      // k_detect_1p takes the first maximum of sqrtf(|D|^2) from a written RD map, and up to three adjacent
+      // floats share one square root (a row's D[d] and D[-d] of equal magnitude differ by an ulp of |D|^2):
+      // lo is the smallest |D|^2 whose magnitude is the row maximum's, so both paths name the same position
+      const float rs = sqrtf(rm);
+      float lo = rm;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const float below = __int_as_float(__float_as_int(lo) - 1);
+        if (lo > 0.f && sqrtf(below) == rs) lo = below;
+      }
       int e = INT_MAX;
 #pragma unroll
       for (int d1s = 15; d1s >= 0; --d1s)
-        if (abs2v(xv[(d1s + 8) & 15]) == rm) e = q + 16 * d1s;
+        if (abs2v(xv[(d1s + 8) & 15]) >= lo) e = q + 16 * d1s;
       e = row_min16(e);
-      a.rowpk[f * NR + r] = make_int2(__float_as_int(sqrtf(rm)), e);   // all lanes of the row: same value
+      a.rowpk[f * NR + r] = make_int2(__float_as_int(rs), e);   // all lanes of the row: same value
     }
   };
 

@@ -130,6 +130,9 @@ int fmcw_ctx_devices(fmcw_ctx* ctx, int32_t* n_devices, int32_t* device_ids, int
  *   range_win   [nts]        = 2*blackman(NTS)
  *   doppler_win [pn]         = 2*chebwin(PN)
  *   calib       [nts] c64    = calib_rx1
+ * Those are the reference's taps; the taps themselves are arbitrary: no kernel assumes a
+ * symmetric window, zero end points, or a calibration vector of constant modulus, linear phase
+ * or zero mean (tests/test_gpu_taps.py runs windows and a calibration with none of these).
  * Also builds the twiddle tables for nr and nd.  Must precede processing and
  * be repeated whenever nts/pn/nr/nd change.  Synchronous with the device: work
  * queued before it (on any stream) finishes with the old taps, and calls after it

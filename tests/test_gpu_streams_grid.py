@@ -233,6 +233,10 @@ def test_pair_access_changes_no_bit(streams, monkeypatch, g, st):
     want_rd = rd_dt == out_dtype
     r = SR.ref(g, FMCW_C64, "synth")
     _taps(streams, r)
+    _pair_identity(streams, monkeypatch, r, cube_dt, rd_dt, out_dtype, want_cube, want_rd)
+
+
+def _pair_identity(streams, monkeypatch, r, cube_dt, rd_dt, out_dtype, want_cube, want_rd):
     monkeypatch.delenv("FMCW_PAIR", raising=False)
     a = _process_device(streams, r, FMCW_C64, out_dtype, want_cube, want_rd)
     monkeypatch.setenv("FMCW_PAIR", "1")
@@ -275,13 +279,17 @@ K1_GRID = [(g, st, cpt) for g in SR.K1_CASES for st in STORAGE for cpt in SR.K1_
 @pytest.mark.parametrize("g,st,cpt", K1_GRID,
                          ids=[f"{SR.case_id(g)}-in_{DT[s[0]]}-cube_{DT[s[1]]}-cpt_{c or 'unset'}" for g, s, c in K1_GRID])
 def test_range_fft_device_grid(engine, monkeypatch, g, st, cpt):
-    import torch
     in_dtype, cube_dtype = st
     if cpt is None:
         monkeypatch.delenv("FMCW_K1_CPT", raising=False)
     else:
         monkeypatch.setenv("FMCW_K1_CPT", cpt)
-    r = SR.ref(g, in_dtype, "synth")
+    _range_fft_device(engine, SR.ref(g, in_dtype, "synth"), in_dtype, cube_dtype, cpt)
+
+
+def _range_fft_device(engine, r, in_dtype, cube_dtype, cpt, label="k1"):
+    import torch
+    g = r.g
     _taps(engine, r)
     nts, pn, nr, nd, F = g
     half = cube_dtype == FMCW_C32H
@@ -302,7 +310,7 @@ def test_range_fft_device_grid(engine, monkeypatch, g, st, cpt):
     e_cube = rel_l2(_complex(d_cube, nr if half else 1), r.plain["cube"], axis=(1, 2))
     # the profile comes from the fp32 registers before the store: the fp32 bar also for a c32h cube
     e_prof = rel_l2(runs[0][1], r.plain["profile"], axis=1)
-    print(f"\nGRID k1 {SR.case_id(g)} in {DT[in_dtype]} cube {DT[cube_dtype]} cpt {cpt or 'unset'} "
+    print(f"\nGRID {label} {SR.case_id(g)} in {DT[in_dtype]} cube {DT[cube_dtype]} cpt {cpt or 'unset'} "
           f"paths {'/'.join(sorted(SR.k1_profile_paths(g, cpt)))} cube {e_cube.max():.2e}/{np.max(emu['e_ref']['cube']):.2e} "
           f"profile {e_prof.max():.2e}")
     assert np.all(e_cube <= SR.bound(emu["e_ref"]["cube"])) and np.all(e_cube <= TOL_FP16_REL_L2)

@@ -23,6 +23,7 @@ from fmcw_radar_processing_amd import params as P
 from oracle import oracle as O
 from tests import detect_reference as DR
 from tests import streams_reference as SR
+from tests import taps_cases as TC
 from tests.helpers import TOL_FP32_REL_L2, rd_rel_err, rel_l2
 from tests.streams_reference import C32H, C64
 
@@ -51,6 +52,8 @@ FP16_NTS = [30, 126, 128, 510, 1000, 1024]
 FULL_HOT_NTS = (126, 1024)             # every chirp position 8 m + w of members m = 0, 1, 31 is hot once
 HOT_SHORT = (0, 1, 7, 8, 9, 255)
 HOT_FULL = tuple(8 * m + w for m in (0, 1, 31) for w in range(8))
+HOT_TAPS, HOT_TAPS_MID = (0, 1, 254, 255), (7, 8, 9)   # the one-hot frames under the non-plain taps of tests/taps_cases.py
+TAPS_TAG = 77                           # seeds the one-hot noise under non-plain taps
 FRAME_COUNTS = [1, 2, 7, 8, 9, 15, 16, 17, 33]
 FRAME_COUNTS_FP16 = (9, 17)
 CHUNK_NTS = [126, 1024]
@@ -89,9 +92,10 @@ def geometry(nts: int):
     return (nts, PN, NR, ND, 2)
 
 
-def build_case(nts: int, **over):
-    """(cfg, p, wr, wd, cal) at nts with detection-parameter overrides; p carries the float32 ABI values."""
-    cfg, p, wr, wd, cal = SR.build_case(geometry(nts))
+def build_case(nts: int, taps="plain", **over):
+    """(cfg, p, wr, wd, cal) at nts with detection-parameter overrides; p carries the float32 ABI values.
+    taps: the family of tests/taps_cases.py."""
+    cfg, p, wr, wd, cal = SR.build_case(geometry(nts), taps=taps)
     if over:
         cfg = dataclasses.replace(cfg, **over)
         p = DR.oracle_params(p, cfg, cfg.max_targets)
@@ -120,53 +124,58 @@ def _cn(rng, shape, sigma):
     return (sigma / np.sqrt(2.0)) * (rng.standard_normal(shape) + 1j * rng.standard_normal(shape))
 
 
-def hot_chirps(nts: int) -> tuple:
+def hot_chirps(nts: int, taps="plain") -> tuple:
+    """The hot chirps of a batch.  Under non-plain taps: both ends of the frame, and 7, 8, 9 (a wave and a
+    member boundary) where those chirps carry Doppler weight (not under `ends`)."""
+    if taps != "plain":
+        return HOT_TAPS if taps == "ends" else tuple(sorted(HOT_TAPS + HOT_TAPS_MID))
     return tuple(sorted(set(HOT_SHORT) | set(HOT_FULL))) if nts in FULL_HOT_NTS else HOT_SHORT
 
 
-def white(nts: int, tag: int) -> np.ndarray:
+def white(nts: int, tag: int, taps="plain") -> np.ndarray:
     """Calibration tone + CN(0, 0.05^2), complex128 [C][S]; tag 7 is streams_reference.noise_frame."""
     rng = np.random.default_rng([nts, PN, NR, ND, tag])
-    return O.synth_cal(nts)[None, :] + _cn(rng, (PN, nts), SR.NOISE_SIGMA)
+    return TC.cal_of(taps, nts)[None, :] + _cn(rng, (PN, nts), SR.NOISE_SIGMA)
 
 
-def white_x0(nts: int, k: int) -> np.ndarray:
+def white_x0(nts: int, k: int, taps="plain") -> np.ndarray:
     """A white frame whose chirp 0 carries 2^k times its own noise, the calibration tone unscaled."""
-    x = white(nts, 9)
-    cal = O.synth_cal(nts)
+    x = white(nts, 9, taps)
+    cal = TC.cal_of(taps, nts)
     x[0] = cal + (2.0 ** k) * (x[0] - cal)
     return x.astype(np.complex64)
 
 
-def one_hot(nts: int, c: int) -> np.ndarray:
+def one_hot(nts: int, c: int, taps="plain") -> np.ndarray:
     """Every chirp the calibration tone, chirp c the calibration tone + CN(0, 0.05^2)."""
-    cal = O.synth_cal(nts)
+    cal = TC.cal_of(taps, nts)
     x = np.broadcast_to(cal[None, :], (PN, nts)).copy()
-    x[c] += _cn(np.random.default_rng([nts, 11, c] + RESEED.get((nts, c), [])), nts, HOT_SIGMA)
+    seed = RESEED.get((nts, c), []) if taps == "plain" else [TAPS_TAG] + TC.RESEED_HOT.get((taps, nts, c), [])
+    x[c] += _cn(np.random.default_rng([nts, 11, c] + seed), nts, HOT_SIGMA)
     return x.astype(np.complex64)
 
 
-def frames(nts: int):
+def frames(nts: int, taps="plain"):
     """(names, iq complex64 [F][C][S]): the batch of one nts, every frame distinct."""
     g = geometry(nts)
-    _, p, *_ = build_case(nts)
+    _, p, *_ = build_case(nts, taps)
     ids = SR.frame_ids(g, p)
     names, out = [], []
     for f in ids:                                                   # 1: one synthetic frame with, one without a target
         A = O.synth_frame_params(f, NR, ND, p["dist_per_bin"])["A"]
         names.append("synth_target" if A > 0 else "synth_empty")
-        out.append(O.synth_frames(1, PN, nts, NR, ND, p["dist_per_bin"], frame0=f)[0])
+        out.append(TC.retone(O.synth_frames(1, PN, nts, NR, ND, p["dist_per_bin"], frame0=f)[0], taps))
     names.append("white")                                           # 2
-    out.append(SR.noise_frame(g)[0])
-    x = white(nts, 8)                                               # 3: chirp 0 the bare calibration tone
-    x[0] = O.synth_cal(nts)
+    out.append(SR.noise_frame(g, taps)[0])
+    x = white(nts, 8, taps)                                         # 3: chirp 0 the bare calibration tone
+    x[0] = TC.cal_of(taps, nts)
     names.append("white_cal0")
     out.append(x.astype(np.complex64))
     names.append("white_x0")                                        # 4
-    out.append(white_x0(nts, K_X0))
-    for c in hot_chirps(nts):                                       # 5
+    out.append(white_x0(nts, k_x0(taps), taps))
+    for c in hot_chirps(nts, taps):                                 # 5
         names.append(f"hot{c}")
-        out.append(one_hot(nts, c))
+        out.append(one_hot(nts, c, taps))
     return names, np.stack(out)
 
 
@@ -205,11 +214,12 @@ def restate_f32(x, cal, p, wr, wd):
     return prof.astype(np.float64), rd.astype(np.complex128)
 
 
-def restate_errors(nts: int, k: int):
-    """(rd, profile, rd_max): the float32 restatement of white_x0(nts, k) against the oracle: the RD map with
-    rd_rel_err's normalisation, the profile's plain L2, and the RD map element-wise, max |d| / rms."""
-    _, p, wr, wd, cal = build_case(nts)
-    x = white_x0(nts, k)
+def restate_errors(nts: int, k: int, taps="plain", frame="white_x0"):
+    """(rd, profile, rd_max): the float32 restatement of white_x0(nts, k), or of the white frame, against the
+    oracle: the RD map with rd_rel_err's normalisation, the profile's plain L2, and the RD map element-wise,
+    max |d| / rms."""
+    _, p, wr, wd, cal = build_case(nts, taps)
+    x = white_x0(nts, k, taps) if frame == "white_x0" else SR.noise_frame(geometry(nts), taps)[0]
     ref = O.process_frames(x[None], cal, p, wr, wd, want_cube=True, want_rd=True, rd_all_rows=True)
     prof, rd = restate_f32(x, cal, p, wr, wd)
     return (float(rd_rel_err(rd[None], ref["rd"], ref["cube"], wd, ND)[0]), float(rel_l2(prof, ref["profile"][0])),
@@ -217,6 +227,11 @@ def restate_errors(nts: int, k: int):
 
 
 K_NTS = (1024, 1000, 126, 30)
+
+
+def k_x0(taps="plain") -> int:
+    """The chirp-0 scale of white_x0 under a family of taps: K_X0, or taps_cases.K_X0 (chosen by choose_k too)."""
+    return K_X0 if taps == "plain" else TC.K_X0[taps]
 
 
 def carries(figs) -> bool:
@@ -227,12 +242,12 @@ def carries(figs) -> bool:
     return max(figs) < 0.5 * TOL_FP32_REL_L2
 
 
-def choose_k():
-    """(k, figures): the largest k <= K_MAX up to which carries() holds at every nts of K_NTS;
-    figures[k][nts] = restate_errors for every k tried."""
-    figs, best = {}, -1
-    for k in range(K_MAX + 1):
-        figs[k] = {nts: restate_errors(nts, k) for nts in K_NTS}
+def choose_k(taps="plain", k_from=0):
+    """(k, figures): the largest k <= K_MAX up to which carries() holds at every nts of K_NTS (tried from
+    k_from on); figures[k][nts] = restate_errors for every k tried."""
+    figs, best = {}, k_from - 1
+    for k in range(k_from, K_MAX + 1):
+        figs[k] = {nts: restate_errors(nts, k, taps) for nts in K_NTS}
         if not all(carries(f) for f in figs[k].values()):
             break
         best = k
@@ -349,9 +364,9 @@ class Ref:
     """One batch: the input as the device holds it, the plain chain, and the emulated chain per
     (mask, rd_dtype).  Shared among tests and never modified by one."""
 
-    def __init__(self, nts, names, iq, in_dtype=C64, probe_column=0, **over):
-        self.nts, self.names = nts, list(names)
-        self.cfg, self.p, self.wr, self.wd, self.cal = build_case(nts, **over)
+    def __init__(self, nts, names, iq, in_dtype=C64, probe_column=0, taps="plain", **over):
+        self.nts, self.names, self.taps = nts, list(names), taps
+        self.cfg, self.p, self.wr, self.wd, self.cal = build_case(nts, taps, **over)
         self.F = iq.shape[0]
         self.probe_column = probe_column
         self.dev_iq, self.iq = SR.iq_as_stored(iq, in_dtype)
@@ -402,12 +417,14 @@ class Ref:
 _refs = {}
 
 
-def ref(nts, in_dtype=C64) -> Ref:
-    """frames(nts) with its probe column on hot chirp 9 (a chirp of member 1, wave 1)."""
-    key = ("nts", nts, in_dtype)
+def ref(nts, in_dtype=C64, taps="plain") -> Ref:
+    """frames(nts) with its probe column on hot chirp 9 (a chirp of member 1, wave 1); on hot chirp 255
+    where the batch has no hot9 (the `ends` taps)."""
+    key = ("nts", nts, in_dtype, taps)
     if key not in _refs:
-        names, iq = frames(nts)
-        _refs[key] = Ref(nts, names, iq, in_dtype, probe_column=names.index("hot9") * PN + 9 + 1)
+        names, iq = frames(nts, taps)
+        c = 9 if "hot9" in names else 255
+        _refs[key] = Ref(nts, names, iq, in_dtype, probe_column=names.index(f"hot{c}") * PN + c + 1, taps=taps)
     return _refs[key]
 
 
@@ -450,12 +467,13 @@ def count_ref(F: int, in_dtype=C64) -> Ref:
     return _refs[key]
 
 
-def fp16_left_out(nts: int, name: str) -> bool:
+def fp16_left_out(nts: int, name: str, taps="plain") -> bool:
     """Whether frame `name` of a batch at nts is left out of the c32h RD comparison (FP16_X0_LEFT_OUT,
     FP16_HOT_LEFT_OUT): its e_ref there is above E_REF_MAX.  Every other frame, the one-hot frames up to
     nts 128 among them, is held at bound(e_ref) per frame and per group; a frame left out still runs, and
     its profile, slow rows, magnitudes and detections are held like everyone's."""
+    x0, hot = (FP16_X0_LEFT_OUT, FP16_HOT_LEFT_OUT) if taps == "plain" else TC.FP16_LEFT_OUT[taps]
     if name == "white_x0":
-        return nts in FP16_X0_LEFT_OUT
-    return name.startswith("hot") and nts in FP16_HOT_LEFT_OUT
+        return nts in x0
+    return name.startswith("hot") and nts in hot
 
