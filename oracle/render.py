@@ -33,17 +33,24 @@ def jet_palette_u8() -> np.ndarray:
 
 
 def render_indices(Q: np.ndarray, nq: int, pmax: float, nfft: int, fs: float, t0: float, dt: float,
-                   W: int, H: int, fmax: float = 150.0, cmin: float = -40.0, cmax: float = 0.0) -> np.ndarray:
-    """Palette indices [H][W] from Q[nseg][nq + 1] (P of bins 0..nq-1, then bin nfft/2)."""
+                   W: int, H: int, fmax: float = 150.0, cmin: float = -40.0, cmax: float = 0.0, details: bool = False):
+    """Palette indices [H][W] from Q[nseg][nq + 1] (P of bins 0..nq-1, then bin nfft/2).
+
+    With details=True returns (indices, d), d holding the per-pixel [H][W] arrays behind them: `ok`
+    (the pixel has an ordinary face), `take` (that face wins the depth test), `m` (its lower bin) and
+    `c0`, `c1` (the stored columns of bins m and m + 1, -1 where Q does not hold the bin)."""
     Q = np.asarray(Q, np.float64)
     nseg = Q.shape[0]
     nb = nfft // 2 + 1
     seam = nb - nb // 2 - 1
     out = np.zeros((H, W), np.uint8)
     if nseg < 2:
+        if details:
+            no, neg = np.zeros((H, W), bool), np.full((H, W), -1, np.int64)
+            return out, dict(ok=no, take=no.copy(), m=neg, c0=neg.copy(), c1=neg.copy())
         return out
     inv = 1.0 / float(np.float32(pmax)) if pmax > 0 else 0.0
-    with np.errstate(divide="ignore"):
+    with np.errstate(divide="ignore", invalid="ignore"):
         Z = np.where(Q > 0, 20.0 * np.log10(Q * inv), -1.0e30)
     Z = np.maximum(Z, -1.0e30)
     px = np.arange(W, dtype=np.float64)
@@ -81,6 +88,8 @@ def render_indices(Q: np.ndarray, nq: int, pmax: float, nfft: int, fs: float, t0
     q = (zc - cmin) / (cmax - cmin) * 256.0
     qf = np.where(q < 0.0, 0.0, np.where(q > 255.0, 255.0, np.floor(q)))
     out[:] = qf.astype(np.uint8)
+    if details:
+        return out, dict(ok=ok, take=take, m=m, c0=c0, c1=c1)
     return out
 
 

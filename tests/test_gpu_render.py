@@ -8,12 +8,17 @@ libfmcw (kernels_render.hip) and written as a palette PNG.
    the float64 oracle's P; fp32 rounding of P may move a colour-index boundary
    or a depth tie, so >= 99.5 % of the pixels agree and no pixel is off by more
    than one colour step except at depth ties (counted separately).
+3. The rules at their seams and holes: RENDER_CASES of tests/test_render_host.py (which proves on the CPU that they
+   reach the seam, the rows above Nyquist, bins Q does not hold, depth-test ties and the -1e30 floor), exact,
+   every byte of the image written; nseg read from the device; the argument checks, the stream and timing stage.
 The pixels are parity-unpinned against MATLAB graphics (not runnable here)."""
 import numpy as np
 import pytest
 
+from fmcw_radar_processing_amd._lib import FmcwError
 from oracle import oracle as O
 from oracle import render as R
+from tests import test_render_host as RH
 
 pytestmark = pytest.mark.gpu
 
@@ -83,3 +88,105 @@ def test_stft_png_end_to_end(engine, tmp_path):
     assert same >= 0.995, same
     far = np.abs(idx.astype(int) - want.astype(int)) > 1
     assert np.mean(far) <= 0.002, np.mean(far)
+
+
+# ---- the kernel against the restatement at its seams, holes and ties ------------------------------------------
+FILL = 0xA5
+
+
+def _render(engine, Q, nq, pmax, nfft, fs, t0, dt, W, H, *, nseg=None, stream=None, img=None, **ptrs):
+    """One fmcw_render_spectrogram_device call into an image pre-filled with 0xA5: [H][1 + W] bytes back.
+    ptrs: d_Q / d_nseg / d_pmax / d_img overridden (None = a NULL pointer)."""
+    import torch
+    t = dict(d_Q=torch.from_numpy(np.array(Q, np.float32)).cuda(),            # a copy: the shared inputs are read-only
+             d_nseg=torch.tensor([len(Q) if nseg is None else nseg], dtype=torch.int64, device="cuda"),
+             d_pmax=torch.tensor([pmax], dtype=torch.float32, device="cuda"),
+             d_img=torch.full((max(H, 1), max(W, 0) + 1), FILL, dtype=torch.uint8, device="cuda") if img is None else img)
+    kept = t["d_img"]
+    t.update(ptrs)
+    try:
+        engine.render_spectrogram_device(t["d_Q"], nq, t["d_nseg"], t["d_pmax"], nfft, fs, t0, dt, W, H, t["d_img"],
+                                         stream=torch.cuda.current_stream() if stream is None else stream)
+    finally:
+        torch.cuda.synchronize()
+    return kept.cpu().numpy()
+
+
+def _assert_picture(img, want):
+    assert np.all(img[:, 0] == 0)                       # the PNG filter byte of every row
+    np.testing.assert_array_equal(img[:, 1:], want)     # and every other byte is an index: nothing keeps the fill
+
+
+@pytest.mark.parametrize("zero_pmax", [False, True], ids=["pmax", "pmax0"])
+@pytest.mark.parametrize("case", RH.RENDER_CASES, ids=RH.case_id)
+def test_render_cases_exact(engine, case, zero_pmax):
+    nfft, fs, nq, nseg, W, H, kind = case
+    Q, pmax, t0, dt, want, _ = RH.reference(case, zero_pmax)
+    img = _render(engine, Q, nq, pmax, nfft, fs, t0, dt, W, H)
+    assert img.shape == (H, W + 1)
+    _assert_picture(img, want)
+
+
+@pytest.mark.parametrize("nseg", [24, 13, 2, 1, 0])
+def test_nseg_is_read_from_the_device(engine, nseg):
+    case = RH.RENDER_CASES[0]
+    nfft, fs, nq, rows, W, H, kind = case
+    Q0, pmax, t0, dt, _, _ = RH.reference(case)
+    assert rows == 24
+    Q = Q0.copy()
+    Q[nseg:] = np.nan                                   # rows past nseg are not read
+    img = _render(engine, Q, nq, pmax, nfft, fs, t0, dt, W, H, nseg=nseg)
+    want = R.render_indices(Q0[:nseg], nq, float(pmax), nfft, fs, t0, dt, W, H)
+    assert want.any() == (nseg >= 2)
+    _assert_picture(img, want)
+
+
+_OK = dict(nfft=64, nq=32, fs=200.0, dt=0.005, W=255, H=97)
+REJECTED = {
+    "nfft-odd": dict(nfft=63), "nfft-0": dict(nfft=0), "nq-0": dict(nq=0), "nq-nfft/2+1": dict(nq=33),
+    "fs-0": dict(fs=0.0), "fs-nan": dict(fs=float("nan")), "dt-0": dict(dt=0.0), "dt-negative": dict(dt=-0.005),
+    "width-0": dict(W=0), "width-65537": dict(W=65537), "height-0": dict(H=0), "height-65536": dict(H=65536),
+    "Q-null": dict(d_Q=None), "nseg-null": dict(d_nseg=None), "pmax-null": dict(d_pmax=None), "img-null": dict(d_img=None),
+}
+
+
+@pytest.mark.parametrize("name", sorted(REJECTED))
+def test_render_rejects(engine, name):
+    """E_ARG before any launch: the image keeps its fill, timing stage `render` counts nothing."""
+    import torch
+    kw = dict(_OK, **REJECTED[name])
+    ptrs = {k: kw.pop(k) for k in list(kw) if k.startswith("d_")}
+    Q, pmax, t0, _, _, _ = RH.reference(RH.RENDER_CASES[0])
+    img = torch.full((_OK["H"], _OK["W"] + 1), FILL, dtype=torch.uint8, device="cuda")   # the buffer a legal call fills
+    engine.timing_reset()
+    engine.timing(1)
+    try:
+        with pytest.raises(FmcwError, match="E_ARG"):
+            _render(engine, Q, kw["nq"], pmax, kw["nfft"], kw["fs"], t0, kw["dt"], kw["W"], kw["H"], img=img, **ptrs)
+        assert engine.timing_read()["render"][1] == 0
+    finally:
+        engine.timing(0)
+        engine.timing_reset()
+    torch.cuda.synchronize()
+    assert np.all(img.cpu().numpy() == FILL)
+
+
+def test_render_stream_and_timing(engine):
+    """A non-default torch stream, with timing stage `render`: one event pair for the one launch."""
+    import torch
+    case = RH.RENDER_CASES[0]
+    nfft, fs, nq, nseg, W, H, kind = case
+    Q, pmax, t0, dt, want, _ = RH.reference(case)
+    s = torch.cuda.Stream()
+    engine.timing_reset()
+    engine.timing(1)
+    try:
+        with torch.cuda.stream(s):
+            img = _render(engine, Q, nq, pmax, nfft, fs, t0, dt, W, H, stream=s)
+        s.synchronize()
+        ms, n = engine.timing_read()["render"]
+        assert n == 1 and ms > 0
+    finally:
+        engine.timing(0)
+        engine.timing_reset()
+    _assert_picture(img, want)
