@@ -1,12 +1,13 @@
 // api_stages.cpp -- the RD-map stages of the libfmcw C-ABI (include/fmcw.h): 2-D CA-CFAR,
-// Doppler-time / range-time signatures, clustering, angle of arrival, tracking and the MTI clutter
-// filter.
+// Doppler-time / range-time signatures, clustering, angle of arrival, tracking, the MTI clutter
+// filter and the combination of the receive channels' maps into beams.
 // Every stage has a host-only fmcw_*_check, a device-pointer entry and a host-pointer entry that
 // shards over the context's devices and walks its shard in chunks; the two entries share the
 // stage's *_entry check.  The rules every stage states alike take the stage's message prefix.
 #include "api_internal.h"
 
 #include <cmath>
+#include <cstring>
 
 namespace {
 
@@ -938,6 +939,192 @@ int fmcw_mti(fmcw_ctx* c, const fmcw_mti_params* q, const void* rd, int32_t rd_d
   return over_devices(c, S, [&](fmcw_ctx* d, int, int64_t s0, int64_t n) {
     return mti_host_one(d, q, static_cast<const char*>(rd) + s0 * F * fin, rd_dtype, n, F, nr, nd,
                         shifted(bg, s0 * cells2), shifted(seen, s0), shifted(static_cast<char*>(out), s0 * F * fin));
+  });
+}
+
+// ---------------------------------------------------------------------------
+// The receive channels' RD maps combined into beams or one integrated map (kernels_beam.hip)
+// ---------------------------------------------------------------------------
+int fmcw_beam_check(const fmcw_beam_params* q, int32_t nr, int32_t nd) {
+  if (!q) return fail(FMCW_E_ARG, "beam params is NULL");
+  CHK(check_rd_shape("beam", nr, nd));
+  if (q->n_chan < 2 || q->n_chan > fmcw::kBeamMax) return fail(FMCW_E_ARG, "beam: n_chan must be in [2, 8]");
+  if (q->n_beam < 1 || q->n_beam > fmcw::kBeamMax) return fail(FMCW_E_ARG, "beam: n_beam must be in [1, 8]");
+  if (q->flags & ~FMCW_BEAM_NCI) return fail(FMCW_E_ARG, "beam: unknown flag bits");
+  if ((q->flags & FMCW_BEAM_NCI) && q->n_beam != 1) return fail(FMCW_E_ARG, "beam: FMCW_BEAM_NCI needs n_beam == 1");
+  for (int b = 0; b < q->n_beam; ++b)
+    for (int a = 0; a < q->n_chan; ++a)
+      if (!std::isfinite(q->w[b][a][0]) || !std::isfinite(q->w[b][a][1]))
+        return fail(FMCW_E_ARG, "beam: the weights must be finite");
+  return FMCW_OK;
+}
+
+int fmcw_beam_steer(int32_t n_chan, int32_t n_beam, float spacing, const float* sin_theta, const float* cal,
+                    const float* taper, int32_t normalize, fmcw_beam_params* q) {
+#pragma clang fp contract(off)
+  if (!q) return fail(FMCW_E_ARG, "beam params is NULL");
+  if (n_chan < 2 || n_chan > fmcw::kBeamMax) return fail(FMCW_E_ARG, "beam: n_chan must be in [2, 8]");
+  if (n_beam < 1 || n_beam > fmcw::kBeamMax) return fail(FMCW_E_ARG, "beam: n_beam must be in [1, 8]");
+  if (!std::isfinite(spacing) || !(std::fabs(spacing) >= 0.01f && std::fabs(spacing) <= 16.f))
+    return fail(FMCW_E_ARG, "beam: spacing must be finite with 0.01 <= |spacing| <= 16");
+  if (!sin_theta) return fail(FMCW_E_ARG, "beam: sin_theta is NULL");
+  for (int b = 0; b < n_beam; ++b)
+    if (!(sin_theta[b] >= -1.f && sin_theta[b] <= 1.f)) return fail(FMCW_E_ARG, "beam: every sin_theta must be in [-1, 1]");
+  if (cal)
+    for (int i = 0; i < 2 * n_chan; ++i)
+      if (!std::isfinite(cal[i])) return fail(FMCW_E_ARG, "beam: cal must be finite");
+  double norm = normalize ? (double)n_chan : 1.0;
+  if (taper) {
+    double sum = 0.0;
+    for (int a = 0; a < n_chan; ++a) {
+      if (!std::isfinite(taper[a])) return fail(FMCW_E_ARG, "beam: taper must be finite");
+      sum = sum + (double)taper[a];
+    }
+    if (normalize && sum == 0.0) return fail(FMCW_E_ARG, "beam: normalize needs a taper whose sum is not 0");
+    if (normalize) norm = sum;
+  }
+  float w[fmcw::kBeamMax][fmcw::kBeamMax][2] = {};
+  for (int b = 0; b < n_beam; ++b)
+    for (int a = 0; a < n_chan; ++a) {
+      // the phase -2 pi spacing a sin(theta) in turns, reduced to [-1/2, 1/2], then split into k whole
+      // quarter turns and a rest f in [-1/2, 1/2] of a quarter turn: f = 0 gives exactly 1 and 0
+      double t = -((double)spacing * (double)a * (double)sin_theta[b]);
+      t = t - std::nearbyint(t);
+      const double q4 = 4.0 * t;
+      const double k = std::nearbyint(q4);
+      const double ang = (q4 - k) * 1.5707963267948966;
+      const double c = std::cos(ang), s = std::sin(ang);
+      double er, ei;
+      switch (((int)k + 4) & 3) {
+        case 0: er = c; ei = s; break;
+        case 1: er = 0.0 - s; ei = c; break;
+        case 2: er = 0.0 - c; ei = 0.0 - s; break;
+        default: er = s; ei = 0.0 - c; break;
+      }
+      const double g = (taper ? (double)taper[a] : 1.0) / norm;
+      const double gr = (cal ? (double)cal[2 * a] : 1.0) * g, gi = (cal ? (double)cal[2 * a + 1] : 0.0) * g;
+      w[b][a][0] = (float)(gr * er - gi * ei);
+      w[b][a][1] = (float)(gr * ei + gi * er);
+      if (!std::isfinite(w[b][a][0]) || !std::isfinite(w[b][a][1]))
+        return fail(FMCW_E_ARG, "beam: a weight does not fit float32");
+    }
+  q->n_chan = n_chan;
+  q->n_beam = n_beam;
+  q->flags = 0;
+  std::memcpy(q->w, w, sizeof(w));
+  return FMCW_OK;
+}
+
+// what both beam entries check: everything but the alignment, which only the device call asks for
+static int beam_entry(fmcw_ctx* c, const fmcw_beam_params* q, const void* const* rd, int32_t rd_dtype, int64_t F, int32_t nr,
+                      int32_t nd, void* const* out) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(fmcw_beam_check(q, nr, nd));
+  CHK(check_rd_dtype(rd_dtype));
+  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
+  if (F > ((int64_t)1 << 40)) return fail(FMCW_E_ARG, "beam: F must be at most 2^40");
+  if (F == 0) return FMCW_OK;
+  if (!rd || !out) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const int A = q->n_chan, B = q->n_beam;
+  for (int a = 0; a < A; ++a)
+    if (!rd[a]) return fail(FMCW_E_ARG, "required pointer is NULL");
+  for (int b = 0; b < B; ++b)
+    if (!out[b]) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const uintptr_t total = (uintptr_t)F * nr * nd * esize(rd_dtype);
+  for (int b = 0; b < B; ++b) {
+    const uintptr_t po = reinterpret_cast<uintptr_t>(out[b]);
+    for (int a = 0; a < A; ++a) {
+      const uintptr_t pa = reinterpret_cast<uintptr_t>(rd[a]);
+      if (po != pa && po < pa + total && pa < po + total)
+        return fail(FMCW_E_ARG, "beam: an output must be one of the inputs itself or not overlap it");
+    }
+    for (int b2 = 0; b2 < b; ++b2) {
+      const uintptr_t p2 = reinterpret_cast<uintptr_t>(out[b2]);
+      if (po == p2) return fail(FMCW_E_ARG, "beam: two outputs at the same address");
+      if (po < p2 + total && p2 < po + total) return fail(FMCW_E_ARG, "beam: the outputs must not overlap each other");
+    }
+  }
+  return FMCW_OK;
+}
+
+int fmcw_beam_device(fmcw_ctx* c, const fmcw_beam_params* q, const void* const* d_rd_ch, int32_t rd_dtype, int64_t F,
+                     int32_t nr, int32_t nd, void* const* d_out, void* stream) {
+  CHK(beam_entry(c, q, d_rd_ch, rd_dtype, F, nr, nd, d_out));
+  if (F == 0) return FMCW_OK;
+  const int A = q->n_chan, B = q->n_beam;
+  for (int a = 0; a < A; ++a)
+    if (reinterpret_cast<uintptr_t>(d_rd_ch[a]) & 15) return fail(FMCW_E_ARG, "beam: every channel's d_rd must be 16-byte aligned");
+  for (int b = 0; b < B; ++b)
+    if (reinterpret_cast<uintptr_t>(d_out[b]) & 15) return fail(FMCW_E_ARG, "beam: every d_out must be 16-byte aligned");
+  CHK(set_device(c));
+  hipStream_t s = pick(c, stream);
+  fmcw::BeamArgs a{};
+  a.A = A; a.B = B;
+  a.h = rd_dtype == FMCW_C32H;
+  a.nci = (q->flags & FMCW_BEAM_NCI) ? 1 : 0;
+  for (int b = 0; b < B; ++b)
+    for (int ch = 0; ch < A; ++ch) {
+      a.w[b][ch][0] = q->w[b][ch][0];
+      a.w[b][ch][1] = q->w[b][ch][1];
+    }
+  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
+  const int64_t f16 = (int64_t)(fin / 16);
+  // one thread per 16-byte piece: at most 2^31 pieces per launch, a grid of fewer than 2^32 threads
+  // (the results do not depend on the cut)
+  const int64_t Fc = ((int64_t)1 << 31) / f16;
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    a.n16 = std::min(Fc, F - f0) * f16;
+    for (int ch = 0; ch < A; ++ch) a.rd[ch] = static_cast<const char*>(d_rd_ch[ch]) + (size_t)f0 * fin;
+    for (int b = 0; b < B; ++b) a.out[b] = static_cast<char*>(d_out[b]) + (size_t)f0 * fin;
+    StageTimer tm(c, 15, s);
+    HIPCHK(fmcw::launch_beam(a, s));
+    tm.done();
+  }
+  return FMCW_OK;
+}
+
+static int beam_host_one(fmcw_ctx* c, const fmcw_beam_params* q, const char* const* rd_ch, int32_t dtype, int64_t F, int32_t nr,
+                         int32_t nd, char* const* out) {
+  CHK(set_device(c));
+  hipStream_t s = c->stream;
+  const int A = q->n_chan, B = q->n_beam;
+  const size_t fin = (size_t)nr * nd * esize(dtype);
+  // all A channels and all B outputs of a chunk are staged
+  const int64_t Fc = host_chunk((size_t)(A + B) * fin, F);
+  CHK(c->bm_rd.ensure((size_t)A * Fc * fin));
+  CHK(c->bm_out.ensure((size_t)B * Fc * fin));
+  char* const dr = c->bm_rd.as<char>();
+  char* const dout = c->bm_out.as<char>();
+  const void* d_ch[fmcw::kBeamMax] = {};
+  void* d_o[fmcw::kBeamMax] = {};
+  for (int ch = 0; ch < A; ++ch) d_ch[ch] = dr + (size_t)ch * Fc * fin;   // a multiple of 256 bytes apart
+  for (int b = 0; b < B; ++b) d_o[b] = dout + (size_t)b * Fc * fin;
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    const int64_t nf = std::min(Fc, F - f0);
+    for (int ch = 0; ch < A; ++ch)
+      HIPCHK(hipMemcpyAsync(dr + (size_t)ch * Fc * fin, rd_ch[ch] + (size_t)f0 * fin, (size_t)nf * fin, hipMemcpyHostToDevice, s));
+    CHK(fmcw_beam_device(c, q, d_ch, dtype, nf, nr, nd, d_o, s));
+    // an output may be one of the inputs: every channel of the chunk is on the device before this
+    for (int b = 0; b < B; ++b)
+      HIPCHK(hipMemcpyAsync(out[b] + (size_t)f0 * fin, dout + (size_t)b * Fc * fin, (size_t)nf * fin, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));           // the chunk buffers are reused by the next chunk
+  }
+  return FMCW_OK;
+}
+
+int fmcw_beam(fmcw_ctx* c, const fmcw_beam_params* q, const void* const* rd_ch, int32_t rd_dtype, int64_t F, int32_t nr,
+              int32_t nd, void* const* out) {
+  CHK(beam_entry(c, q, rd_ch, rd_dtype, F, nr, nd, out));
+  if (F == 0) return FMCW_OK;
+  const int A = q->n_chan, B = q->n_beam;
+  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
+  // frames are independent: contiguous shards, each written in place
+  return over_devices(c, F, [&](fmcw_ctx* d, int, int64_t f0, int64_t n) {
+    const char* ch0[fmcw::kBeamMax] = {};
+    char* o0[fmcw::kBeamMax] = {};
+    for (int ch = 0; ch < A; ++ch) ch0[ch] = static_cast<const char*>(rd_ch[ch]) + (size_t)f0 * fin;
+    for (int b = 0; b < B; ++b) o0[b] = static_cast<char*>(out[b]) + (size_t)f0 * fin;
+    return beam_host_one(d, q, ch0, rd_dtype, n, nr, nd, o0);
   });
 }
 

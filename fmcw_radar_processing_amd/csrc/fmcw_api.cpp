@@ -1,6 +1,6 @@
 // fmcw_api.cpp -- libfmcw C-ABI (include/fmcw.h) on top of the gfx950 kernels: the context
 // and the per-frame pipeline.  The STFT and render path is api_stft.cpp, the RD-map stages
-// (CFAR, signatures, clustering, tracking, MTI) are api_stages.cpp; api_internal.h holds what
+// (CFAR, signatures, clustering, tracking, MTI, beams) are api_stages.cpp; api_internal.h holds what
 // the three share.
 //
 // Host responsibilities kept here, mirroring what radar_processing.m does

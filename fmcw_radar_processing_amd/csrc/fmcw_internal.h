@@ -425,6 +425,19 @@ struct MtiArgs {
 bool mti_ring_ok(int ring);
 hipError_t launch_mti(const MtiArgs& a, hipStream_t s);
 
+// The receive channels' RD maps combined into beamformed or channel-integrated maps (kernels_beam.hip): k_beam
+constexpr int kBeamMax = 8;            // channels and beams at most
+struct BeamArgs {
+  const void* rd[kBeamMax];        // channel a: the launch's frames, [F][NR][ND] c64 or c32h; 16-byte aligned
+  void* out[kBeamMax];             // beam b: the same shape and dtype; may be one of rd (in place)
+  int64_t n16;                     // 16-byte pieces of one map of the launch: F * (frame bytes / 16)
+  int A, B;                        // channels 2..kBeamMax, beams 1..kBeamMax (1 when nci)
+  int h;                           // fp16 storage
+  int nci;                         // non-coherent integration: out[0] = (sqrt(sum |t_a|^2), +0)
+  float w[kBeamMax][kBeamMax][2];  // (re, im) per (beam, channel)
+};
+hipError_t launch_beam(const BeamArgs& a, hipStream_t s);
+
 bool range_size_supported(int nr);
 bool doppler_size_supported(int nd);
 

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import FMCW_C32H, FMCW_C64, STAGES, FmcwError, check
-from .params import AoaConfig, CfarConfig, ClusterConfig, FmcwConfig, MtiConfig, SigConfig, TrackConfig
+from .params import AoaConfig, BeamConfig, CfarConfig, ClusterConfig, FmcwConfig, MtiConfig, SigConfig, TrackConfig
 
 
 def _ptr(a) -> ct.c_void_p:
@@ -651,6 +651,60 @@ class Engine:
                             probe_column=probe_column, stream=stream)
         self.mti_device(q, d_rd, out_dtype, 1, F, cfg.nr, cfg.nd, d_bg, d_seen, d_out=d_rd if d_out is None else d_out,
                         stream=stream)
+
+    # ---- the receive channels combined into beams (include/fmcw.h, fmcw_beam_params) -----------
+    @staticmethod
+    def beam_weights(n_chan: int, sin_theta, spacing: float = 0.5, cal=None, taper=None,
+                     normalize: bool = True) -> np.ndarray:
+        """fmcw_beam_steer: complex64 [n_beam][n_chan], the weights of one beam per entry of
+        sin_theta for a uniform line of n_chan elements `spacing` wavelengths apart, in the sign
+        convention of AoaConfig.spacing.  cal: the per-channel complex calibration weights a caller
+        gives aoa; taper: a real weight per channel; normalize: divide by the taper's sum (n_chan
+        without one).  Feed the result to BeamConfig."""
+        st = np.ascontiguousarray(np.atleast_1d(sin_theta), np.float32)
+        c = None if cal is None else np.ascontiguousarray(
+            np.asarray(cal, np.complex64).reshape(-1)).view(np.float32)
+        t = None if taper is None else np.ascontiguousarray(np.asarray(taper, np.float32).reshape(-1))
+        if (c is not None and c.size != 2 * int(n_chan)) or (t is not None and t.size != int(n_chan)):
+            raise ValueError("beam_weights: cal and taper need one value per channel")
+        q = _lib.BeamParams()
+        check(_lib.load().fmcw_beam_steer(int(n_chan), int(st.size), float(spacing), _ptr(st), _ptr(c), _ptr(t),
+                                          1 if normalize else 0, ct.byref(q)))
+        w = np.array(q.w[:], np.float32).reshape(8, 8, 2)[:st.size, :int(n_chan)]
+        return np.ascontiguousarray(w).view(np.complex64).reshape(st.size, int(n_chan))
+
+    def beam(self, rds, q: BeamConfig) -> list:
+        """The q.n_beam maps combined from the q.n_chan RD maps `rds`, one per receive channel, each
+        complex64 [F][nr][nd] or float16 [F][nr][nd][2] holding D / (nr nd), all of one dtype and
+        shape.  Host arrays, frames sharded over the context's devices.  Returns a list of q.n_beam
+        new arrays of the inputs' shape and dtype (with q.nci: one map, the amplitude sqrt(sum of the
+        weighted channels' powers) in the real part)."""
+        chans = [_host_rd(rd, "F") for rd in rds]
+        if len(chans) != int(q.n_chan):
+            raise ValueError("beam: rds must hold q.n_chan maps")
+        dt = chans[0][1]
+        if any(c[1] != dt or c[0].shape != chans[0][0].shape for c in chans):
+            raise ValueError("beam: the channels must share one dtype and shape")
+        F, nr, nd = chans[0][0].shape[:3]
+        outs = [np.empty_like(chans[0][0]) for _ in range(int(q.n_beam))]
+        qa = q.abi()
+        ptrs = (ct.c_void_p * len(chans))(*[c[0].ctypes.data for c in chans])
+        optrs = (ct.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+        check(self.lib.fmcw_beam(self.h, ct.byref(qa), ptrs, dt, F, nr, nd, optrs))
+        return outs
+
+    def beam_device(self, q: BeamConfig, d_rds, rd_dtype: int, F: int, nr: int, nd: int, d_outs, stream=None) -> None:
+        """fmcw_beam_device: d_rds the q.n_chan device RD maps [F][nr][nd] of rd_dtype and d_outs the
+        q.n_beam device maps of the same shape and dtype to write (separate allocations or slices of
+        one, each 16-byte aligned; an output may be one of the inputs itself: in place).  q: a
+        BeamConfig, or the C struct _lib.BeamParams itself.  cfar_device, signature_device,
+        mti_device and aoa_device chain on an output as on any RD buffer.  Asynchronous on `stream`."""
+        qa = q.abi() if hasattr(q, "abi") else q
+        ptrs = (ct.c_void_p * max(len(d_rds), 1))(*[_ptr(d).value or 0 for d in d_rds])
+        optrs = (ct.c_void_p * max(len(d_outs), 1))(*[_ptr(d).value or 0 for d in d_outs])
+        with _sided(stream) as hs:
+            check(self.lib.fmcw_beam_device(self.h, ct.byref(qa), ptrs, int(rd_dtype), int(F), int(nr), int(nd), optrs,
+                                            hs))
 
     # ---- timing -----------------------------------------------------------------
     def timing(self, level: int) -> None:

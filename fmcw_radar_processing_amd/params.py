@@ -12,8 +12,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import windows
-from ._lib import (FMCW_CFAR_LOCAL_MAX, FMCW_MTI_FREEZE, FMCW_MTI_RAMP, FMCW_SIG_DB, AoaParams, CfarParams,
-                   ClusterParams, MtiParams, Params, SigParams, TrackParams)
+from ._lib import (FMCW_BEAM_NCI, FMCW_CFAR_LOCAL_MAX, FMCW_MTI_FREEZE, FMCW_MTI_RAMP, FMCW_SIG_DB, AoaParams,
+                   BeamParams, CfarParams, ClusterParams, MtiParams, Params, SigParams, TrackParams)
 
 C0 = 3e8  # radar_processing.m:67
 
@@ -492,3 +492,57 @@ class MtiConfig:
             lam = np.float32(self.lambda_)
         if not (np.isfinite(lam) and 0 < lam <= 1):
             raise ValueError("mti: lambda must be finite and in (0, 1]")
+
+
+@dataclass
+class BeamConfig:
+    """fmcw_beam_params (include/fmcw.h): the receive channels' RD maps combined into n_beam maps.
+    weights holds one complex weight per (beam, channel), [n_beam][n_chan] (Engine.beam_weights forms
+    those of a uniform line).  nci: non-coherent integration, one map of sqrt(sum |w_a x_a|^2) from
+    weights[0]; it needs n_beam 1."""
+    weights: np.ndarray
+    nci: bool = False
+
+    def __post_init__(self):
+        w = np.asarray(self.weights)
+        if w.ndim != 2:
+            raise ValueError("beam: weights must be [n_beam][n_chan] complex")
+        with np.errstate(over="ignore"):
+            self.weights = w.astype(np.complex64)
+
+    @property
+    def n_beam(self) -> int:
+        return self.weights.shape[0]
+
+    @property
+    def n_chan(self) -> int:
+        return self.weights.shape[1]
+
+    def abi(self) -> BeamParams:
+        B, A = self.weights.shape
+        if B > 8 or A > 8:
+            raise ValueError("beam: at most 8 beams of 8 channels")
+        w = np.zeros((8, 8, 2), np.float32)
+        w[:B, :A, 0], w[:B, :A, 1] = self.weights.real, self.weights.imag
+        q = BeamParams(A, B, FMCW_BEAM_NCI if self.nci else 0)
+        q.w[:] = w.reshape(-1).tolist()
+        return q
+
+    def weights_f32(self) -> np.ndarray:
+        """float32 [n_beam][n_chan][2]: the weights as the C struct carries them."""
+        return np.ascontiguousarray(self.weights).view(np.float32).reshape(self.n_beam, self.n_chan, 2)
+
+    def validate(self, nr: int, nd: int) -> None:
+        """The rules of fmcw_beam_check; ValueError naming the first one violated."""
+        if nr < 16 or nr > 2048 or nr & (nr - 1):
+            raise ValueError("beam: nr must be a power of two in [16, 2048]")
+        if nd < 4 or nd > 1024 or nd & (nd - 1):
+            raise ValueError("beam: nd must be a power of two in [4, 1024]")
+        if not 2 <= self.n_chan <= 8:
+            raise ValueError("beam: n_chan must be in [2, 8]")
+        if not 1 <= self.n_beam <= 8:
+            raise ValueError("beam: n_beam must be in [1, 8]")
+        if self.nci and self.n_beam != 1:
+            raise ValueError("beam: FMCW_BEAM_NCI needs n_beam == 1")
+        if not np.isfinite(self.weights_f32()).all():
+            raise ValueError("beam: the weights must be finite")

@@ -53,7 +53,9 @@ extern "C" {
  *    + the clutter-filter entry points (fmcw_mti_check, fmcw_mti_ring, fmcw_mti_device, fmcw_mti),
  *    the struct fmcw_mti_params and timing stage 13, added within ABI 4 in the same way
  *    + the angle-of-arrival entry points (fmcw_aoa_check, fmcw_aoa_device, fmcw_aoa), the structs
- *    fmcw_aoa_params / fmcw_angles and timing stage 14, added within ABI 4 in the same way */
+ *    fmcw_aoa_params / fmcw_angles and timing stage 14, added within ABI 4 in the same way
+ *    + the channel-combining entry points (fmcw_beam_check, fmcw_beam_steer, fmcw_beam_device,
+ *    fmcw_beam), the struct fmcw_beam_params and timing stage 15, added within ABI 4 in the same way */
 #define FMCW_ABI_VERSION 4
 
 typedef enum fmcw_status {
@@ -285,7 +287,8 @@ int fmcw_synth_device(fmcw_ctx* ctx, const fmcw_params* p, int64_t frame0, int64
  *        launch pair of fmcw_cfar_device), 11 cluster (one pair per k_cluster launch of
  *        fmcw_cluster_device), 12 track (one pair per k_track launch of fmcw_track_device),
  *        13 mti (one pair per fmcw_mti_device call's k_mti + k_mti_seen launches), 14 aoa (one pair
- *        per k_aoa launch of fmcw_aoa_device).
+ *        per k_aoa launch of fmcw_aoa_device), 15 beam (one pair per k_beam launch of
+ *        fmcw_beam_device).
  *        fmcw_timing_read synchronises. */
 int fmcw_timing_enable(fmcw_ctx* ctx, int32_t enable);
 int fmcw_timing_read(fmcw_ctx* ctx, int32_t stage, double* total_ms, int64_t* launches);
@@ -832,6 +835,91 @@ int fmcw_mti_device(fmcw_ctx* ctx, const fmcw_mti_params* q, const void* d_rd, i
  * guarantee above).  Returns when the outputs are on the host. */
 int fmcw_mti(fmcw_ctx* ctx, const fmcw_mti_params* q, const void* rd, int32_t rd_dtype,
              int64_t S, int64_t F, int32_t nr, int32_t nd, float* bg, int32_t* seen, void* out);
+
+/* ---------------------------------------------------------------------------
+ * Receive channels combined: beamformed and channel-integrated RD maps (added within ABI 4; beyond
+ * the reference, which parses numAntennasRx, :103, and keeps only frame.Chirp(:,:,1), :202).  The A
+ * channels' maps become B maps to detect on: B steered beams (coherent), or one map of the summed
+ * channel power (non-coherent integration).  Every output is an RD map in the layout and dtype of the
+ * input, so fmcw_mti*, fmcw_cfar*, fmcw_sig*, clustering, fmcw_aoa* and tracking take it unchanged.
+ *   Input: A channel maps rd[a], a = 0..A-1, A in 2..8, each [F][nr][nd] in the layout fmcw_process*
+ *     writes, all of one dtype, FMCW_C64 or FMCW_C32H; nr, nd within CFAR's limits.  The maps are
+ *     given as a host array of A pointers (for the device call: device pointers, each 16-byte
+ *     aligned; the array itself is read on the host); separate allocations or slices of one, exactly
+ *     as fmcw_aoa takes them.
+ *   Output: B maps out[b], b = 0..B-1, B in 1..8, of the same shape and dtype, given as a host array
+ *     of B pointers.  out[b] may be exactly one of the rd[a] (in place); any partial overlap of an
+ *     output with an input or with another output, and two outputs at the same address, are
+ *     FMCW_E_ARG.
+ *   Parameters: n_chan = A, n_beam = B; flags 0 (coherent) or FMCW_BEAM_NCI, which needs n_beam == 1;
+ *     an unknown flag bit is FMCW_E_ARG; w[b][a], a complex float32 weight (re, im) per (beam,
+ *     channel), finite; entries with a >= A or b >= B are ignored.
+ *   One cell, coherent, in float32, every operation rounded on its own in the order written (no fused
+ *   multiply-add).  For every beam b:
+ *   1. x_a is the stored value of channel a; fp16 storage is widened exactly.
+ *      t_a.re = x.re w.re - x.im w.im;  t_a.im = x.re w.im + x.im w.re,  with w = w[b][a].
+ *   2. y = t_0; then y.re = y.re + t_a.re, y.im = y.im + t_a.im for a = 1..A-1, in ascending a.
+ *   3. out[b] = y; for FMCW_C32H it is converted with IEEE round-to-nearest-even, subnormals kept,
+ *      overflow to +-inf (exactly numpy's astype(float16)).
+ *   One cell, FMCW_BEAM_NCI: t_a as above with w[0][a]; p = (t_0.re^2 + t_0.im^2), then
+ *   p = p + (t_a.re^2 + t_a.im^2) in ascending a; out[0].re = sqrtf(p), correctly rounded,
+ *   out[0].im = +0.  This is an amplitude map: CFAR's |.|^2 of it is the summed channel power to
+ *   within rounding.  (It stays in the RD layout so that every later stage takes it; the unused
+ *   imaginary half of the one written map is the price.)
+ *   Results are bit-identical from call to call and do not depend on F, on sharding or on chunking.  A
+ *   non-finite stored value or weight makes that cell's outputs unspecified; it touches nothing else.
+ *   Measured on one MI355X over 4096 frames of 1024 x 256 per map, channel a = one RD map turned by
+ *   0.6 a rad (profiles/beam_bench.json, 2026-10-21, tree e759450+), beside fmcw_copy_device over
+ *   (A + B) / 2 maps' bytes in the same run, which reads and writes exactly the bytes the stage reads
+ *   and writes; stage / copy in ms, complex64 then fp16 storage: (A, B) = (2, 1) 3.94 / 3.95 and
+ *   1.94 / 1.96, (2, 1) NCI 3.93 / 3.94 and 1.94 / 1.96, (4, 4) 10.42 / 10.48 (complex64) MEET the
+ *   copy-time yardstick, as does (2, 1) in place in fp16 storage, 1.95 / 1.96; (2, 1) in place in
+ *   complex64 3.98 / 3.95, (4, 1) 6.77 / 6.49 and 3.40 / 3.27, (4, 4) fp16 5.32 / 5.22, (8, 1) 12.90 /
+ *   11.86 and 6.35 / 5.86, (8, 8) complex64 21.41 / 20.95 MISS it by 1-9 %, and (8, 8) in fp16 storage
+ *   14.92 / 10.55 MISSES it by 41 %: there the arithmetic, not HBM, sets the time.
+ * ------------------------------------------------------------------------- */
+enum { FMCW_BEAM_NCI = 1 };
+typedef struct fmcw_beam_params {
+  int32_t n_chan;          /* A, 2..8 */
+  int32_t n_beam;          /* B, 1..8; 1 with FMCW_BEAM_NCI */
+  int32_t flags;           /* 0 or FMCW_BEAM_NCI */
+  float   w[8][8][2];      /* w[b][a]: (re, im) of beam b, channel a */
+} fmcw_beam_params;
+
+/* Host only, no context: FMCW_E_ARG (with a message) for any violation of the constraints. */
+int fmcw_beam_check(const fmcw_beam_params* q, int32_t nr, int32_t nd);
+
+/* Host only, no context: the weights of n_beam beams of a uniform line of n_chan elements, in the
+ * convention of fmcw_aoa: channel a of a source at sin(theta) carries the phase
+ * +2 pi spacing a sin(theta).  spacing as fmcw_aoa_params.spacing (wavelengths, signed, finite,
+ * 0.01 <= |spacing| <= 16); sin_theta [n_beam], each in [-1, 1]; cal [n_chan][2] (re, im), the
+ * per-channel calibration weights a caller gives fmcw_aoa, finite, or NULL (1); taper [n_chan], real,
+ * finite, or NULL (1); normalize != 0 divides by sum taper_a (which must then not be 0), or by n_chan
+ * without a taper, so that a plane wave from the look direction comes out at channel amplitude and
+ * fp16 storage does not overflow.
+ *   w[b][a] = cal_a (taper_a / norm) exp(-j 2 pi spacing a sin(theta_b)),
+ * formed in double and rounded once to float32: t = -((double)spacing a sin_theta_b) in turns,
+ * t = t - nearbyint(t), k = nearbyint(4 t), phi = (4 t - k) pi/2, e = (cos phi, sin phi) turned by k
+ * exact quarter turns; g = cal_a (taper_a / norm); w = (g.re e.re - g.im e.im, g.re e.im + g.im e.re).
+ * So every phase that is a whole number of quarter turns gives exactly 0 and +-1.
+ * Sets q->n_chan, q->n_beam, q->flags = 0 and all of q->w (unused entries 0).  FMCW_E_ARG (with a
+ * message, q untouched) for any violated constraint or a weight that does not fit float32. */
+int fmcw_beam_steer(int32_t n_chan, int32_t n_beam, float spacing, const float* sin_theta, const float* cal,
+                    const float* taper, int32_t normalize, fmcw_beam_params* q);
+
+/* Device pointers (d_rd_ch[a] and d_out[b] are device pointers, each 16-byte aligned; the two arrays
+ * and *q are read on the host), asynchronous on `stream`; needs no fmcw_set_taps.  Acts on the
+ * context's first device.  F = 0 is a no-op.  FMCW_E_ARG is returned before any launch: the outputs
+ * are then untouched.  In place is safe: a lane of k_beam stores only to the 16 bytes it has itself
+ * loaded from every input. */
+int fmcw_beam_device(fmcw_ctx* ctx, const fmcw_beam_params* q, const void* const* d_rd_ch, int32_t rd_dtype,
+                     int64_t F, int32_t nr, int32_t nd, void* const* d_out, void* stream);
+
+/* Host pointers (no alignment asked for): staged (all A channels and B outputs of a chunk), frames
+ * sharded over the context's devices and chunked as fmcw_cfar is (bit-identical shards and chunks);
+ * returns when the outputs are on the host. */
+int fmcw_beam(fmcw_ctx* ctx, const fmcw_beam_params* q, const void* const* rd_ch, int32_t rd_dtype, int64_t F,
+              int32_t nr, int32_t nd, void* const* out);
 
 /* ---------------------------------------------------------------------------
  * spectrogram.png, replacing radar_processing.m:331-348:

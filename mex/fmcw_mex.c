@@ -74,7 +74,20 @@
  *                                        nseq, single complex (reshape(out, Nd, Nr, []) feeds 'cfar' and 'signature'
  *                                        unchanged), seen 1 x nseq.  With FMCW_MTI_FREEZE in Q.flags bg and seen
  *                                        come back as they went in.
- *   fmcw_mex('close')                                             -> fmcw_ctx_destroy
+ *   out = fmcw_mex('beam', Q, rd4)                                -> fmcw_beam: the receive planes' RD maps combined
+ *                                        into B maps to detect on (beyond the reference): steered beams, or with
+ *                                        FMCW_BEAM_NCI in Q.flags one map of the summed plane power; Q: a struct with
+ *                                        the fields flags and w, a real double array of 2 x A x B values (re, im;
+ *                                        plane; beam), e.g. what 'beam_steer' returns; rd4 as for 'aoa', single
+ *                                        complex Nd x Nr x F x A; out is (Nd*Nr*F) x B, single complex:
+ *                                        reshape(out, Nd, Nr, F, B) is the 4-D array Nd x Nr x F x B, and
+ *                                        out4(:, :, :, b) feeds 'mti', 'cfar' and 'signature' unchanged
+ *   w = fmcw_mex('beam_steer', n_chan, spacing, sin_theta[, cal, taper, normalize])
+ *                                                                 -> fmcw_beam_steer (needs no context): the weights of
+ *                                        one beam per entry of sin_theta for a uniform line, in the sign convention
+ *                                        of 'aoa'; cal: 2 A doubles (re, im per plane) or [], taper: A doubles or [],
+ *                                        normalize: 0 / 1 (default 1); w is (2*A) x B, double, the layout of Q.w
+ *   fmcw_mex('close')                                            -> fmcw_ctx_destroy
  *
  * P is a struct with the fields of fmcw_params (nts, pn, nr, nd, max_targets,
  * doppler_fallback_idx, if_scale, range_thr, doppler_thr, min_d, max_d,
@@ -209,6 +222,35 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     int64_t bytes = 0;
     check(fmcw_json_write(path, fl, nf, 1, 0, &bytes));
     if (nlhs > 0) plhs[0] = mxCreateDoubleScalar((double)bytes);
+    return;
+  }
+  if (!strcmp(cmd, "beam_steer")) {         /* w = fmcw_mex('beam_steer', n_chan, spacing, sin_theta[, cal, taper, normalize]): needs no context */
+    if (nrhs < 4 || nrhs > 7) mexErrMsgIdAndTxt("fmcw:arg", "beam_steer: n_chan, spacing, sin_theta[, cal, taper, normalize]");
+    const int32_t A = (int32_t)mxGetScalar(prhs[1]);
+    const mwSize B = mxGetNumberOfElements(prhs[3]);
+    if (A < 2 || A > 8 || B < 1 || B > 8 || !mxIsDouble(prhs[3]) || mxIsComplex(prhs[3]))
+      mexErrMsgIdAndTxt("fmcw:arg", "beam_steer: n_chan in 2..8 and sin_theta a real double vector of 1..8 values");
+    float st[8], cal[16], taper[8];
+    const float* pc = NULL;
+    const float* pt = NULL;
+    for (mwSize b = 0; b < B; ++b) st[b] = (float)mxGetDoubles(prhs[3])[b];
+    if (nrhs > 4 && mxGetNumberOfElements(prhs[4]) > 0) {
+      if (!mxIsDouble(prhs[4]) || mxIsComplex(prhs[4]) || mxGetNumberOfElements(prhs[4]) != (mwSize)(2 * A))
+        mexErrMsgIdAndTxt("fmcw:arg", "beam_steer: cal must be a real double array of 2 A values (re, im per plane)");
+      for (int i = 0; i < 2 * A; ++i) cal[i] = (float)mxGetDoubles(prhs[4])[i];
+      pc = cal;
+    }
+    if (nrhs > 5 && mxGetNumberOfElements(prhs[5]) > 0) {
+      if (!mxIsDouble(prhs[5]) || mxIsComplex(prhs[5]) || mxGetNumberOfElements(prhs[5]) != (mwSize)A)
+        mexErrMsgIdAndTxt("fmcw:arg", "beam_steer: taper must be a real double array of A values");
+      for (int i = 0; i < A; ++i) taper[i] = (float)mxGetDoubles(prhs[5])[i];
+      pt = taper;
+    }
+    fmcw_beam_params q;
+    check(fmcw_beam_steer(A, (int32_t)B, (float)mxGetScalar(prhs[2]), st, pc, pt, nrhs > 6 ? mxGetScalar(prhs[6]) != 0 : 1, &q));
+    plhs[0] = mxCreateDoubleMatrix((mwSize)(2 * A), B, mxREAL);
+    for (mwSize b = 0; b < B; ++b)
+      for (int i = 0; i < 2 * A; ++i) mxGetDoubles(plhs[0])[b * (mwSize)(2 * A) + i] = q.w[b][i / 2][i % 2];
     return;
   }
   if (!g_ctx) mexErrMsgIdAndTxt("fmcw:state", "call fmcw_mex('init') first");
@@ -540,6 +582,38 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                    mxGetInt32s(seen), mxGetComplexSingles(plhs[0])));
     if (nlhs > 1) plhs[1] = bg;
     if (nlhs > 2) plhs[2] = seen;
+    return;
+  }
+  if (!strcmp(cmd, "beam")) {               /* out = fmcw_mex('beam', Q, rd4) */
+    if (nrhs != 3) mexErrMsgIdAndTxt("fmcw:arg", "beam: Q, rd4");
+    const mxArray* s = prhs[1];
+    const mxArray* rd = prhs[2];
+    if (!mxIsStruct(s)) mexErrMsgIdAndTxt("fmcw:arg", "Q must be a struct");
+    if (!mxIsSingle(rd) || !mxIsComplex(rd) || mxGetNumberOfDimensions(rd) != 4)
+      mexErrMsgIdAndTxt("fmcw:arg", "rd4 must be single complex Nd x Nr x F x A");
+    const mwSize* dims = mxGetDimensions(rd);
+    const int32_t nd = (int32_t)dims[0], nr = (int32_t)dims[1];
+    const int64_t F = (int64_t)dims[2];
+    const mwSize A = dims[3];
+    const mxArray* w = mxGetField(s, 0, "w");
+    if (A < 2 || A > 8 || !w || !mxIsDouble(w) || mxIsComplex(w) || mxGetNumberOfElements(w) == 0 ||
+        mxGetNumberOfElements(w) % (2 * A) || mxGetNumberOfElements(w) > 16 * A)
+      mexErrMsgIdAndTxt("fmcw:arg", "A must be in 2..8 and Q.w a real double array of 2 x A x B values (re, im; plane; beam), B in 1..8");
+    fmcw_beam_params q;
+    memset(&q, 0, sizeof q);
+    q.n_chan = (int32_t)A;
+    q.n_beam = (int32_t)(mxGetNumberOfElements(w) / (2 * A));
+    q.flags = (int32_t)field(s, "flags");
+    for (int b = 0; b < q.n_beam; ++b)
+      for (mwSize i = 0; i < 2 * A; ++i) q.w[b][i / 2][i % 2] = (float)mxGetDoubles(w)[(mwSize)b * 2 * A + i];
+    check(fmcw_beam_check(&q, nr, nd));
+    const size_t map = (size_t)F * (size_t)nr * (size_t)nd;
+    plhs[0] = mxCreateNumericMatrix((mwSize)map, (mwSize)q.n_beam, mxSINGLE_CLASS, mxCOMPLEX);
+    const void* chan[8] = {0};
+    void* out[8] = {0};
+    for (mwSize a = 0; a < A; ++a) chan[a] = mxGetComplexSingles(rd) + a * map;
+    for (int b = 0; b < q.n_beam; ++b) out[b] = mxGetComplexSingles(plhs[0]) + (size_t)b * map;
+    check(fmcw_beam(g_ctx, &q, chan, FMCW_C64, F, nr, nd, out));
     return;
   }
   mexErrMsgIdAndTxt("fmcw:arg", "unknown command '%s'", cmd);
