@@ -20,7 +20,7 @@ FMCW_PIPE_AUTO, FMCW_PIPE_STREAMS, FMCW_PIPE_ONEPASS, FMCW_PIPE_XCD = 0, 1, 3, 4
 ABI_VERSION = 4
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_HIP", -3: "E_OOM", -4: "E_STATE", -5: "E_DATA"}
 STAGES = ("range", "doppler", "detect", "compact", "stft_power", "stft_db", "range_only", "range_doppler", "onepass",
-          "render", "cfar", "cluster", "track", "mti", "aoa", "beam")
+          "render", "cfar", "cluster", "track", "mti", "aoa", "beam", "oscfar")
 FMCW_CFAR_LOCAL_MAX = 1
 FMCW_SIG_DB = 1
 FMCW_MTI_RAMP, FMCW_MTI_FREEZE = 1, 2
@@ -50,6 +50,11 @@ class CfarParams(ct.Structure):
         ("r_lo", ct.c_int32), ("r_hi", ct.c_int32), ("max_det", ct.c_int32), ("flags", ct.c_int32),
         ("alpha", ct.c_float),
     ]
+
+
+class OsCfarParams(ct.Structure):
+    """fmcw_oscfar_params (include/fmcw.h)."""
+    _fields_ = [("win", CfarParams), ("rank", ct.c_int32)]
 
 
 class SigParams(ct.Structure):
@@ -172,6 +177,11 @@ SIGNATURES = {
     "fmcw_cfar_device": (ct.c_int, [_P, ct.POINTER(CfarParams), _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P,
                                     _P]),
     "fmcw_cfar": (ct.c_int, [_P, ct.POINTER(CfarParams), _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "fmcw_oscfar_check": (ct.c_int, [ct.POINTER(OsCfarParams), _I32, _I32, ct.POINTER(_I32)]),
+    "fmcw_oscfar_alpha": (ct.c_int, [_I32, _I32, _D, ct.POINTER(_F)]),
+    "fmcw_oscfar_device": (ct.c_int, [_P, ct.POINTER(OsCfarParams), _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P,
+                                      _P]),
+    "fmcw_oscfar": (ct.c_int, [_P, ct.POINTER(OsCfarParams), _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "fmcw_sig_check": (ct.c_int, [ct.POINTER(SigParams), _I32, _I32]),
     "fmcw_sig_device": (ct.c_int, [_P, ct.POINTER(SigParams), _P, _I32, _I64, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P]),
     "fmcw_sig_db_device": (ct.c_int, [_P, _P, _I64, _P, _F, _P, _P]),

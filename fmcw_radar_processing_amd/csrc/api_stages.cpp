@@ -1,4 +1,4 @@
-// api_stages.cpp -- the RD-map stages of the libfmcw C-ABI (include/fmcw.h): 2-D CA-CFAR,
+// api_stages.cpp -- the RD-map stages of the libfmcw C-ABI (include/fmcw.h): 2-D CA-CFAR and OS-CFAR,
 // Doppler-time / range-time signatures, clustering, angle of arrival, tracking, the MTI clutter
 // filter and the combination of the receive channels' maps into beams.
 // Every stage has a host-only fmcw_*_check, a device-pointer entry and a host-pointer entry that
@@ -184,9 +184,10 @@ int fmcw_cfar_device(fmcw_ctx* c, const fmcw_cfar_params* q, const void* d_rd, i
   return FMCW_OK;
 }
 
-static int cfar_host_one(fmcw_ctx* c, const fmcw_cfar_params* q, const char* rd, int32_t dtype, int64_t F, int32_t nr,
-                         int32_t nd, int32_t* count, int32_t* ridx, int32_t* didx, float* power, float* noise,
-                         uint8_t* mask) {
+// os: the OS-CFAR parameters whose window q is (fmcw_oscfar), or nullptr for CA-CFAR
+static int cfar_host_one(fmcw_ctx* c, const fmcw_cfar_params* q, const fmcw_oscfar_params* os, const char* rd,
+                         int32_t dtype, int64_t F, int32_t nr, int32_t nd, int32_t* count, int32_t* ridx, int32_t* didx,
+                         float* power, float* noise, uint8_t* mask) {
   CHK(set_device(c));
   hipStream_t s = c->stream;
   const int K = q->max_det;
@@ -204,10 +205,14 @@ static int cfar_host_one(fmcw_ctx* c, const fmcw_cfar_params* q, const char* rd,
   for (int64_t f0 = 0; f0 < F; f0 += Fc) {
     const int64_t nf = std::min(Fc, F - f0);
     HIPCHK(hipMemcpyAsync(c->cf_in.p, rd + (size_t)f0 * fin, (size_t)nf * fin, hipMemcpyHostToDevice, s));
-    CHK(fmcw_cfar_device(c, q, c->cf_in.p, dtype, nf, nr, nd, reinterpret_cast<int32_t*>(o + oo[0]) + f0,
-                         reinterpret_cast<int32_t*>(o + oo[1]) + f0 * K, reinterpret_cast<int32_t*>(o + oo[2]) + f0 * K,
-                         reinterpret_cast<float*>(o + oo[3]) + f0 * K, reinterpret_cast<float*>(o + oo[4]) + f0 * K,
-                         mask ? c->cf_mask.as<uint8_t>() : nullptr, s));
+    int32_t* const dc = reinterpret_cast<int32_t*>(o + oo[0]) + f0;
+    int32_t* const dri = reinterpret_cast<int32_t*>(o + oo[1]) + f0 * K;
+    int32_t* const ddi = reinterpret_cast<int32_t*>(o + oo[2]) + f0 * K;
+    float* const dpw = reinterpret_cast<float*>(o + oo[3]) + f0 * K;
+    float* const dnz = reinterpret_cast<float*>(o + oo[4]) + f0 * K;
+    uint8_t* const dm = mask ? c->cf_mask.as<uint8_t>() : nullptr;
+    if (os) CHK(fmcw_oscfar_device(c, os, c->cf_in.p, dtype, nf, nr, nd, dc, dri, ddi, dpw, dnz, dm, s));
+    else CHK(fmcw_cfar_device(c, q, c->cf_in.p, dtype, nf, nr, nd, dc, dri, ddi, dpw, dnz, dm, s));
     if (mask) HIPCHK(hipMemcpyAsync(mask + (size_t)f0 * fmask, c->cf_mask.p, (size_t)nf * fmask, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));           // the chunk buffers are reused by the next chunk
   }
@@ -225,7 +230,124 @@ int fmcw_cfar(fmcw_ctx* c, const fmcw_cfar_params* q, const void* rd, int32_t rd
   const int K = q->max_det;
   // frames are independent: contiguous shards, each written in place
   return over_devices(c, F, [&](fmcw_ctx* d, int, int64_t f0, int64_t n) {
-    return cfar_host_one(d, q, static_cast<const char*>(rd) + (size_t)f0 * fin, rd_dtype, n, nr, nd, count + f0,
+    return cfar_host_one(d, q, nullptr, static_cast<const char*>(rd) + (size_t)f0 * fin, rd_dtype, n, nr, nd, count + f0,
+                         ridx + f0 * K, didx + f0 * K, power + f0 * K, noise + f0 * K, shifted(mask, f0 * nr * nd));
+  });
+}
+
+// ---------------------------------------------------------------------------
+// 2-D OS-CFAR over the RD map (kernels_oscfar.hip)
+// ---------------------------------------------------------------------------
+int fmcw_oscfar_check(const fmcw_oscfar_params* q, int32_t nr, int32_t nd, int32_t* n_train_full) {
+  if (!q) return fail(FMCW_E_ARG, "oscfar params is NULL");
+  int32_t n = 0;
+  CHK(fmcw_cfar_check(&q->win, nr, nd, &n));
+  if (q->rank < 1 || q->rank > n)
+    return fail(FMCW_E_ARG, "oscfar: rank must be in [1, " + std::to_string(n) + "], the full window's training cells");
+  if (n_train_full) *n_train_full = n;
+  return FMCW_OK;
+}
+
+// what both OS-CFAR entries check before they look at F == 0 and the pointers
+static int oscfar_entry(fmcw_ctx* c, const fmcw_oscfar_params* q, int32_t rd_dtype, int64_t F, int32_t nr, int32_t nd,
+                        int32_t* n_train_full) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(fmcw_oscfar_check(q, nr, nd, n_train_full));
+  CHK(check_rd_dtype(rd_dtype));
+  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
+  return FMCW_OK;
+}
+
+int fmcw_oscfar_alpha(int32_t n_train, int32_t rank, double pfa, float* alpha) {
+  if (!alpha) return fail(FMCW_E_ARG, "alpha is NULL");
+  if (n_train < 1) return fail(FMCW_E_ARG, "oscfar: n_train must be >= 1");
+  if (rank < 1 || rank > n_train) return fail(FMCW_E_ARG, "oscfar: rank must be in [1, n_train]");
+  if (!(pfa > 0.0 && pfa < 1.0)) return fail(FMCW_E_ARG, "oscfar: pfa must be in (0, 1)");
+  // -ln Pfa(alpha) = sum_{i < k} log1p(alpha / (N - i)) rises with alpha: bracket, then bisect
+  const double want = -std::log(pfa);
+  auto g = [&](double a) {
+    double s = 0.0;
+    for (int i = 0; i < rank; ++i) s += std::log1p(a / (double)(n_train - i));
+    return s;
+  };
+  double lo = 0.0, hi = 1.0;
+  while (g(hi) < want) {
+    lo = hi;
+    hi *= 2.0;
+  }
+  for (int it = 0; it < 200 && hi - lo > 0.0; ++it) {
+    const double mid = 0.5 * (lo + hi);
+    if (mid <= lo || mid >= hi) break;
+    if (g(mid) < want) lo = mid;
+    else hi = mid;
+  }
+  *alpha = (float)(0.5 * (lo + hi));
+  return FMCW_OK;
+}
+
+int fmcw_oscfar_device(fmcw_ctx* c, const fmcw_oscfar_params* q, const void* d_rd, int32_t rd_dtype, int64_t F,
+                       int32_t nr, int32_t nd, int32_t* d_count, int32_t* d_ridx, int32_t* d_didx, float* d_power,
+                       float* d_noise, uint8_t* d_mask, void* stream) {
+  int32_t nfull = 0;
+  CHK(oscfar_entry(c, q, rd_dtype, F, nr, nd, &nfull));
+  if (F == 0) return FMCW_OK;
+  if (!d_rd || !d_count || !d_ridx || !d_didx || !d_power || !d_noise) return fail(FMCW_E_ARG, "required pointer is NULL");
+  if (reinterpret_cast<uintptr_t>(d_rd) & 15) return fail(FMCW_E_ARG, "oscfar: d_rd must be 16-byte aligned");
+  CHK(set_device(c));
+  hipStream_t s = pick(c, stream);
+  fmcw::OsCfarArgs o{};
+  fmcw::CfarArgs& a = o.c;
+  o.rank = q->rank;
+  o.nfull = nfull;
+  a.h = rd_dtype == FMCW_C32H;
+  a.scale = a.h ? (float)nr * (float)nd : 1.f;
+  a.NR = nr; a.ND = nd;
+  a.gr = q->win.guard_r; a.gd = q->win.guard_d; a.tr = q->win.train_r; a.td = q->win.train_d;
+  gate_rows(q->win.r_lo, q->win.r_hi, nr, a.g0, a.g1);
+  a.K = q->win.max_det;
+  a.local_max = (q->win.flags & FMCW_CFAR_LOCAL_MAX) ? 1 : 0;
+  a.alpha = q->win.alpha;
+  fmcw::cfar_plan(a, F);
+  // frames per launch group: CA-CFAR's list scratch, budget and override (fmcw_cfar_device)
+  const size_t per = fmcw::cfar_scratch_per_frame(a);
+  size_t budget = (size_t)256 << 20;
+  if (const char* e = std::getenv("FMCW_CFAR_SCRATCH"); e && std::atoll(e) > 0) budget = (size_t)std::atoll(e);
+  const int64_t Fc = std::max<int64_t>(1, std::min<int64_t>({F, (int64_t)(budget / per), (int64_t)32768}));
+  const size_t nsub = (size_t)a.strips * a.tiles * a.waves;
+  const size_t list_bytes = (size_t)Fc * nsub * a.K * sizeof(float4);
+  int st = FMCW_OK;
+  char* scr = static_cast<char*>(c->cfar_scr.get(s, list_bytes + (size_t)Fc * nsub * 4, &st));
+  CHK(st);
+  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    a.F = std::min(Fc, F - f0);
+    a.rd = static_cast<const char*>(d_rd) + (size_t)f0 * fin;
+    a.sub_list = reinterpret_cast<float4*>(scr);
+    a.sub_count = reinterpret_cast<int32_t*>(scr + list_bytes);
+    a.det_count = d_count + f0;
+    a.det_ridx = d_ridx + f0 * a.K;
+    a.det_didx = d_didx + f0 * a.K;
+    a.det_power = d_power + f0 * a.K;
+    a.det_noise = d_noise + f0 * a.K;
+    a.mask = d_mask ? d_mask + (size_t)f0 * nr * nd : nullptr;
+    StageTimer tm(c, 16, s);
+    HIPCHK(fmcw::launch_oscfar(o, s));
+    tm.done();
+  }
+  CHK(c->cfar_scr.done(s));
+  return FMCW_OK;
+}
+
+int fmcw_oscfar(fmcw_ctx* c, const fmcw_oscfar_params* q, const void* rd, int32_t rd_dtype, int64_t F, int32_t nr,
+                int32_t nd, int32_t* count, int32_t* ridx, int32_t* didx, float* power, float* noise, uint8_t* mask) {
+  CHK(oscfar_entry(c, q, rd_dtype, F, nr, nd, nullptr));
+  if (F == 0) return FMCW_OK;
+  if (!rd || !count || !ridx || !didx || !power || !noise) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
+  const int K = q->win.max_det;
+  // frames are independent: contiguous shards, each written in place
+  return over_devices(c, F, [&](fmcw_ctx* d, int, int64_t f0, int64_t n) {
+    return cfar_host_one(d, &q->win, q, static_cast<const char*>(rd) + (size_t)f0 * fin, rd_dtype, n, nr, nd, count + f0,
                          ridx + f0 * K, didx + f0 * K, power + f0 * K, noise + f0 * K, shifted(mask, f0 * nr * nd));
   });
 }

@@ -310,6 +310,16 @@ struct CfarArgs {
 void cfar_plan(CfarArgs& a, int64_t F);
 size_t cfar_scratch_per_frame(const CfarArgs& a);
 hipError_t launch_cfar(const CfarArgs& a, hipStream_t s);
+hipError_t launch_cfar_gather(const CfarArgs& a, hipStream_t s);
+
+// 2-D OS-CFAR over the RD map (kernels_oscfar.hip): k_oscfar + k_cfar_gather + k_oscfar_select.
+// c is planned by cfar_plan and uses CA's scratch layout; its list entries' noise slot stays 0.
+struct OsCfarArgs {
+  CfarArgs c;
+  int rank;                // 1..nfull, the caller's rank in the full window
+  int nfull;               // training cells of the full window
+};
+hipError_t launch_oscfar(const OsCfarArgs& a, hipStream_t s);
 
 // Doppler-time / range-time signatures of the RD map (kernels_sig.hip): k_sig + k_sig_gather, k_sig_db
 struct SigArgs {

@@ -290,4 +290,14 @@ hipError_t launch_cfar(const CfarArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// k_cfar_gather alone, over lists another kernel wrote in k_cfar's format under a cfar_plan that
+// the caller checked as launch_cfar does (kernels_oscfar.hip)
+hipError_t launch_cfar_gather(const CfarArgs& a, hipStream_t s) {
+  if (a.F <= 0) return hipSuccess;
+  if (a.strips < 1 || a.strips > kCfarMaxStrips || a.strips * a.tiles * a.waves > kCfarMaxSub || a.F > 0x7fffffffLL)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_cfar_gather, dim3((unsigned)a.F), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 }  // namespace fmcw

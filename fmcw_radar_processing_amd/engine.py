@@ -17,7 +17,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import FMCW_C32H, FMCW_C64, STAGES, FmcwError, check
-from .params import AoaConfig, BeamConfig, CfarConfig, ClusterConfig, FmcwConfig, MtiConfig, SigConfig, TrackConfig
+from .params import (AoaConfig, BeamConfig, CfarConfig, ClusterConfig, FmcwConfig, MtiConfig, OsCfarConfig, SigConfig,
+                     TrackConfig)
 
 
 def _ptr(a) -> ct.c_void_p:
@@ -252,8 +253,9 @@ class Engine:
                                              hs))
 
     # ---- 2-D CA-CFAR over the RD map (include/fmcw.h, fmcw_cfar_params) ---------
-    def cfar(self, rd: np.ndarray, q: CfarConfig, want_mask: bool = False) -> dict:
-        """Detections of rd: complex64 [F][nr][nd], or float16 [F][nr][nd][2] holding D / (nr nd).
+    def cfar(self, rd: np.ndarray, q: CfarConfig | OsCfarConfig, want_mask: bool = False) -> dict:
+        """Detections of rd (fmcw_cfar, or fmcw_oscfar for an OsCfarConfig): complex64 [F][nr][nd],
+        or float16 [F][nr][nd][2] holding D / (nr nd).
         Host arrays, sharded over the context's devices.  Returns det_count [F], det_range_idx,
         det_doppler_idx, det_power, det_noise [F][max_det] (1-based indices, 0 where unused) and,
         once set_taps has given the geometry's scales, range_m / speed_mps of every listed
@@ -266,9 +268,10 @@ class Engine:
                    det_noise=np.zeros((F, max(K, 0)), np.float32))
         mask = np.zeros((F, nr, nd), np.uint8) if want_mask else None
         qa = q.abi()
-        check(self.lib.fmcw_cfar(self.h, ct.byref(qa), _ptr(rd), dt, F, nr, nd, _ptr(out["det_count"]),
-                                 _ptr(out["det_range_idx"]), _ptr(out["det_doppler_idx"]), _ptr(out["det_power"]),
-                                 _ptr(out["det_noise"]), _ptr(mask)))
+        call = self.lib.fmcw_oscfar if isinstance(q, OsCfarConfig) else self.lib.fmcw_cfar
+        check(call(self.h, ct.byref(qa), _ptr(rd), dt, F, nr, nd, _ptr(out["det_count"]),
+                   _ptr(out["det_range_idx"]), _ptr(out["det_doppler_idx"]), _ptr(out["det_power"]),
+                   _ptr(out["det_noise"]), _ptr(mask)))
         if mask is not None:
             out["mask"] = mask
         if self.cfg is not None and (self.cfg.nr, self.cfg.nd) == (nr, nd):
@@ -277,20 +280,22 @@ class Engine:
             out["speed_mps"] = np.where(used, self.cfg.speed(out["det_doppler_idx"]), np.nan)
         return out
 
-    def cfar_device(self, q: CfarConfig, d_rd, rd_dtype: int, F: int, nr: int, nd: int, outs: dict, d_mask=None,
-                    stream=None) -> None:
-        """fmcw_cfar_device: d_rd [F][nr][nd] of rd_dtype on the device; outs holds the device
+    def cfar_device(self, q: CfarConfig | OsCfarConfig, d_rd, rd_dtype: int, F: int, nr: int, nd: int, outs: dict,
+                    d_mask=None, stream=None) -> None:
+        """fmcw_cfar_device (fmcw_oscfar_device for an OsCfarConfig): d_rd [F][nr][nd] of rd_dtype on
+        the device; outs holds the device
         buffers det_count [F] int32, det_range_idx / det_doppler_idx [F][max_det] int32 and
         det_power / det_noise [F][max_det] float32.  Asynchronous on `stream`."""
         qa = q.abi()
+        call = self.lib.fmcw_oscfar_device if isinstance(q, OsCfarConfig) else self.lib.fmcw_cfar_device
         with _sided(stream) as hs:
-            check(self.lib.fmcw_cfar_device(self.h, ct.byref(qa), _ptr(d_rd), int(rd_dtype), int(F), int(nr), int(nd),
-                                            _ptr(outs["det_count"]), _ptr(outs["det_range_idx"]),
-                                            _ptr(outs["det_doppler_idx"]), _ptr(outs["det_power"]),
-                                            _ptr(outs["det_noise"]), _ptr(d_mask), hs))
+            check(call(self.h, ct.byref(qa), _ptr(d_rd), int(rd_dtype), int(F), int(nr), int(nd),
+                       _ptr(outs["det_count"]), _ptr(outs["det_range_idx"]), _ptr(outs["det_doppler_idx"]),
+                       _ptr(outs["det_power"]), _ptr(outs["det_noise"]), _ptr(d_mask), hs))
 
-    def process_cfar_device(self, d_iq, F: int, in_dtype: int, outs: dict, q: CfarConfig, d_rd, cfar_outs: dict,
-                            out_dtype: int = FMCW_C64, d_mask=None, d_cube=None, probe_column: int = 0,
+    def process_cfar_device(self, d_iq, F: int, in_dtype: int, outs: dict, q: CfarConfig | OsCfarConfig, d_rd,
+                            cfar_outs: dict, out_dtype: int = FMCW_C64, d_mask=None, d_cube=None,
+                            probe_column: int = 0,
                             stream=None) -> None:
         """IQ in, detections out, on one stream with no host round trip: process_device writing the
         RD map to d_rd (out_dtype), then cfar_device over it."""
@@ -300,6 +305,31 @@ class Engine:
         self.process_device(d_iq, F, in_dtype, outs, d_cube=d_cube, d_rd=d_rd, out_dtype=out_dtype,
                             probe_column=probe_column, stream=stream)
         self.cfar_device(q, d_rd, out_dtype, F, cfg.nr, cfg.nd, cfar_outs, d_mask=d_mask, stream=stream)
+
+    # ---- 2-D OS-CFAR over the RD map (include/fmcw.h, fmcw_oscfar_params) -------
+    # cfar, cfar_device and process_cfar_device dispatch on the parameters' type, and with them
+    # targets, angles, process_targets_device and process_tracks_device; these names say it aloud.
+    def oscfar(self, rd: np.ndarray, q: OsCfarConfig, want_mask: bool = False) -> dict:
+        """fmcw_oscfar: the dict of `cfar`, det_noise holding the order statistic X_(k)."""
+        if not isinstance(q, OsCfarConfig):
+            raise TypeError("oscfar needs an OsCfarConfig")
+        return self.cfar(rd, q, want_mask=want_mask)
+
+    def oscfar_device(self, q: OsCfarConfig, d_rd, rd_dtype: int, F: int, nr: int, nd: int, outs: dict, d_mask=None,
+                      stream=None) -> None:
+        """fmcw_oscfar_device, with the buffers of `cfar_device`.  Asynchronous on `stream`."""
+        if not isinstance(q, OsCfarConfig):
+            raise TypeError("oscfar_device needs an OsCfarConfig")
+        self.cfar_device(q, d_rd, rd_dtype, F, nr, nd, outs, d_mask=d_mask, stream=stream)
+
+    def process_oscfar_device(self, d_iq, F: int, in_dtype: int, outs: dict, q: OsCfarConfig, d_rd, cfar_outs: dict,
+                              out_dtype: int = FMCW_C64, d_mask=None, d_cube=None, probe_column: int = 0,
+                              stream=None) -> None:
+        """IQ in, OS-CFAR detections out, on one stream with no host round trip."""
+        if not isinstance(q, OsCfarConfig):
+            raise TypeError("process_oscfar_device needs an OsCfarConfig")
+        self.process_cfar_device(d_iq, F, in_dtype, outs, q, d_rd, cfar_outs, out_dtype=out_dtype, d_mask=d_mask,
+                                 d_cube=d_cube, probe_column=probe_column, stream=stream)
 
     # ---- Doppler-time / range-time signatures of the RD map (include/fmcw.h, fmcw_sig_params) ----
     def signature(self, rd: np.ndarray, q: SigConfig, center: np.ndarray | None = None) -> dict:
@@ -417,7 +447,7 @@ class Engine:
                                                _ptr(det["det_doppler_idx"]), _ptr(det["det_power"]),
                                                _ptr(det.get("det_noise")), ct.byref(t), _ptr(d_det_label), hs))
 
-    def targets(self, rd: np.ndarray, q_cfar: CfarConfig, q_cluster: ClusterConfig) -> dict:
+    def targets(self, rd: np.ndarray, q_cfar: CfarConfig | OsCfarConfig, q_cluster: ClusterConfig) -> dict:
         """cfar then cluster over rd (host arrays): the dict of `cluster`, with the detection lists
         of `cfar` under their own names."""
         det = self.cfar(rd, q_cfar)
@@ -427,8 +457,9 @@ class Engine:
             out[k] = det[k]
         return out
 
-    def process_targets_device(self, d_iq, F: int, in_dtype: int, outs: dict, q_cfar: CfarConfig, d_rd,
-                               cfar_outs: dict, q_cluster: ClusterConfig, tgt_outs: dict, d_det_label=None,
+    def process_targets_device(self, d_iq, F: int, in_dtype: int, outs: dict,
+                               q_cfar: CfarConfig | OsCfarConfig, d_rd, cfar_outs: dict,
+                               q_cluster: ClusterConfig, tgt_outs: dict, d_det_label=None,
                                out_dtype: int = FMCW_C64, d_mask=None, d_cube=None, probe_column: int = 0,
                                stream=None) -> None:
         """IQ in, targets out, on one stream with no host round trip: process_cfar_device (RD map to
@@ -495,7 +526,8 @@ class Engine:
                                            int(max_det), _ptr(det["det_count"]), _ptr(det["det_range_idx"]),
                                            _ptr(det["det_doppler_idx"]), _ptr(d_det_label), ct.byref(t), hs))
 
-    def angles(self, rds, q_cfar: CfarConfig, q_cluster: ClusterConfig, q_aoa: AoaConfig, det_chan: int = 0) -> dict:
+    def angles(self, rds, q_cfar: CfarConfig | OsCfarConfig, q_cluster: ClusterConfig, q_aoa: AoaConfig,
+               det_chan: int = 0) -> dict:
         """cfar on channel det_chan, cluster, then aoa over all channels (host arrays): the three
         dicts merged, plus angle_deg [F][max_det] and tgt_angle_deg [F][max_tgt], degrees(arcsin(sin))
         formed on the host."""
@@ -577,8 +609,9 @@ class Engine:
                                              _ptr(tgts["peak_power"]), _ptr(d_state), ct.byref(t), _ptr(d_tgt_track),
                                              hs))
 
-    def process_tracks_device(self, d_iq, F: int, in_dtype: int, outs: dict, q_cfar: CfarConfig, d_rd, cfar_outs: dict,
-                              q_cluster: ClusterConfig, tgt_outs: dict, q_track: TrackConfig, d_state, trk_outs: dict,
+    def process_tracks_device(self, d_iq, F: int, in_dtype: int, outs: dict,
+                              q_cfar: CfarConfig | OsCfarConfig, d_rd, cfar_outs: dict, q_cluster: ClusterConfig,
+                              tgt_outs: dict, q_track: TrackConfig, d_state, trk_outs: dict,
                               d_tgt_track=None, d_det_label=None, out_dtype: int = FMCW_C64, d_mask=None, d_cube=None,
                               probe_column: int = 0, stream=None) -> None:
         """IQ in, tracks out, on one stream with no host round trip: process_targets_device (targets

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import windows
 from ._lib import (FMCW_BEAM_NCI, FMCW_CFAR_LOCAL_MAX, FMCW_MTI_FREEZE, FMCW_MTI_RAMP, FMCW_SIG_DB, AoaParams,
-                   BeamParams, CfarParams, ClusterParams, MtiParams, Params, SigParams, TrackParams)
+                   BeamParams, CfarParams, ClusterParams, MtiParams, OsCfarParams, Params, SigParams, TrackParams)
 
 C0 = 3e8  # radar_processing.m:67
 
@@ -160,6 +160,60 @@ class CfarConfig:
             raise ValueError("no range bin lies in [min_d, max_d]")
         q.r_lo, q.r_hi = int(sel[0]) + 1, int(sel[-1]) + 1
         q.alpha = cls.alpha_for(q.n_train_full, pfa)
+        return q
+
+
+@dataclass
+class OsCfarConfig:
+    """fmcw_oscfar_params (include/fmcw.h): 2-D ordered-statistic CFAR over the RD map.  CfarConfig's
+    window, gate and list fields; `rank` in 1..n_train_full picks the order statistic X_(k) of the
+    training powers (scaled to the clipped window near the range edges); alpha is the linear power
+    ratio of the test P > alpha * X_(k)."""
+    guard_r: int = 1
+    guard_d: int = 1
+    train_r: int = 2
+    train_d: int = 2
+    alpha: float = 1.0
+    r_lo: int = 0
+    r_hi: int = 0
+    max_det: int = 64
+    local_max: bool = False
+    rank: int = 1
+
+    @property
+    def n_train_full(self) -> int:
+        wr, wd = self.guard_r + self.train_r, self.guard_d + self.train_d
+        return (2 * wr + 1) * (2 * wd + 1) - (2 * self.guard_r + 1) * (2 * self.guard_d + 1)
+
+    def abi(self) -> OsCfarParams:
+        win = CfarParams(self.guard_r, self.guard_d, self.train_r, self.train_d, self.r_lo, self.r_hi, self.max_det,
+                         FMCW_CFAR_LOCAL_MAX if self.local_max else 0, self.alpha)
+        return OsCfarParams(win, self.rank)
+
+    @staticmethod
+    def alpha_for(n_train: int, rank: int, pfa: float) -> float:
+        """fmcw_oscfar_alpha: the alpha with prod_{i<rank} (N - i) / (N - i + alpha) = pfa, as the
+        float32 the C-ABI carries."""
+        import ctypes as ct
+
+        from . import _lib
+        a = ct.c_float()
+        _lib.check(_lib.load().fmcw_oscfar_alpha(int(n_train), int(rank), float(pfa), ct.byref(a)))
+        return float(a.value)
+
+    @classmethod
+    def for_config(cls, cfg: "FmcwConfig", pfa: float = 1e-3, guard=(1, 1), train=(2, 2), rank_share: float = 0.75,
+                   max_det: int = 64, local_max: bool = False) -> "OsCfarConfig":
+        """The detector for cfg's RD map: CfarConfig.for_config's gate (the peak rule's),
+        rank = max(1, floor(rank_share * n_train_full)) and the alpha of that rank for pfa."""
+        q = cls(guard_r=int(guard[0]), guard_d=int(guard[1]), train_r=int(train[0]), train_d=int(train[1]),
+                max_det=int(max_det), local_max=bool(local_max))
+        sel = gate_bins(cfg)
+        if len(sel) == 0:
+            raise ValueError("no range bin lies in [min_d, max_d]")
+        q.r_lo, q.r_hi = int(sel[0]) + 1, int(sel[-1]) + 1
+        q.rank = max(1, int(np.floor(rank_share * q.n_train_full)))
+        q.alpha = cls.alpha_for(q.n_train_full, q.rank, pfa)
         return q
 
 

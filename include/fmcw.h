@@ -55,7 +55,10 @@ extern "C" {
  *    + the angle-of-arrival entry points (fmcw_aoa_check, fmcw_aoa_device, fmcw_aoa), the structs
  *    fmcw_aoa_params / fmcw_angles and timing stage 14, added within ABI 4 in the same way
  *    + the channel-combining entry points (fmcw_beam_check, fmcw_beam_steer, fmcw_beam_device,
- *    fmcw_beam), the struct fmcw_beam_params and timing stage 15, added within ABI 4 in the same way */
+ *    fmcw_beam), the struct fmcw_beam_params and timing stage 15, added within ABI 4 in the same way
+ *    + the ordered-statistic CFAR entry points (fmcw_oscfar_check, fmcw_oscfar_alpha,
+ *    fmcw_oscfar_device, fmcw_oscfar), the struct fmcw_oscfar_params and timing stage 16, added
+ *    within ABI 4 in the same way */
 #define FMCW_ABI_VERSION 4
 
 typedef enum fmcw_status {
@@ -288,7 +291,8 @@ int fmcw_synth_device(fmcw_ctx* ctx, const fmcw_params* p, int64_t frame0, int64
  *        fmcw_cluster_device), 12 track (one pair per k_track launch of fmcw_track_device),
  *        13 mti (one pair per fmcw_mti_device call's k_mti + k_mti_seen launches), 14 aoa (one pair
  *        per k_aoa launch of fmcw_aoa_device), 15 beam (one pair per k_beam launch of
- *        fmcw_beam_device).
+ *        fmcw_beam_device), 16 oscfar (one pair per k_oscfar + k_cfar_gather + k_oscfar_select
+ *        launch group of fmcw_oscfar_device).
  *        fmcw_timing_read synchronises. */
 int fmcw_timing_enable(fmcw_ctx* ctx, int32_t enable);
 int fmcw_timing_read(fmcw_ctx* ctx, int32_t stage, double* total_ms, int64_t* launches);
@@ -392,6 +396,61 @@ int fmcw_cfar_device(fmcw_ctx* ctx, const fmcw_cfar_params* q, const void* d_rd,
 int fmcw_cfar(fmcw_ctx* ctx, const fmcw_cfar_params* q, const void* rd, int32_t rd_dtype, int64_t F,
               int32_t nr, int32_t nd, int32_t* det_count, int32_t* det_range_idx,
               int32_t* det_doppler_idx, float* det_power, float* det_noise, uint8_t* mask);
+
+/* ---------------------------------------------------------------------------
+ * 2-D ordered-statistic CFAR (OS-CFAR) over the range-Doppler map (added within ABI 4).  The
+ * cell-averaging threshold above is the window's mean, so one strong return in a neighbour's
+ * window lifts that neighbour's threshold by P_strong / N and hides a weak target next to it; an
+ * order statistic of the window does not move.  Window, gate, flags, list format and mask are
+ * fmcw_cfar's (`win`, under fmcw_cfar_check's constraints).  Indices below are 0-based; every
+ * index the calls return is 1-based.
+ *   Power: P[r][d] = fl(fl(re re) + fl(im im)) of the stored value in float32, every operation
+ *     rounded on its own (no fused multiply-add).  fp16 storage is widened exactly and multiplied
+ *     by (float)nr (float)nd (a power of two, exact) before squaring.  k_cfar may contract its
+ *     multiply-add, so these powers may differ from fmcw_cfar's det_power in the last bit.
+ *   Training set: exactly fmcw_cfar's.  N_full is the full window's count, N(r) row r's clipped one.
+ *   Rank: `rank` in 1..N_full.  Row r uses k(r) = 1 + ((rank - 1) (N(r) - 1)) / (N_full - 1) by
+ *     integer division (k = 1 when N_full = 1): 1 -> 1, N_full -> N(r), a clipped window keeps the
+ *     same quantile.
+ *   Test: a gated cell is a detection iff #{training cells x : fl(alpha x) < P} >= k(r).  fl(alpha .)
+ *     is monotone, so this is exactly P > fl(alpha X_(k)), X_(k) the k-th smallest training power
+ *     (ties counted): compares only, no sort and no float sum.
+ *   FMCW_CFAR_LOCAL_MAX keeps its meaning.
+ *   Outputs as for fmcw_cfar: det_count, the lists (ascending (range, doppler), cut at max_det
+ *     while the count is full, 0 where unused) and the optional mask (not cut).  det_power = P;
+ *     det_noise = X_(k), one of the input powers bit for bit.  The lists feed fmcw_cluster*,
+ *     fmcw_aoa* and the rest unchanged.
+ *   With finite input every output byte equals a float32 evaluation of the rules above, for any F
+ *   and however a host call is sharded or chunked.  A non-finite stored value makes the outcome of
+ *   the cells whose window holds it unspecified and touches nothing else.
+ *   Measured on one MI355X: DESIGN.md 4.11 (profiles/oscfar_bench.json).
+ * ------------------------------------------------------------------------- */
+typedef struct fmcw_oscfar_params {
+  fmcw_cfar_params win;    /* window, gate, max_det, flags and alpha, under fmcw_cfar's rules */
+  int32_t rank;            /* 1..N_full */
+} fmcw_oscfar_params;
+
+/* Host only, no context.  fmcw_oscfar_check: fmcw_cfar_check on `win`, then 1 <= rank <= N_full;
+ * FMCW_E_ARG with a message for any violation; on success *n_train_full (may be NULL) = N_full.
+ * fmcw_oscfar_alpha: for exponentially distributed noise power the k-th of N training powers gives
+ * Pfa = prod_{i=0}^{k-1} (N - i) / (N - i + alpha); solved for alpha in double precision (bisection
+ * on ln Pfa) and returned as float.  FMCW_E_ARG unless 0 < pfa < 1 and 1 <= rank <= n_train. */
+int fmcw_oscfar_check(const fmcw_oscfar_params* q, int32_t nr, int32_t nd, int32_t* n_train_full);
+int fmcw_oscfar_alpha(int32_t n_train, int32_t rank, double pfa, float* alpha);
+
+/* Device pointers (d_rd 16-byte aligned), asynchronous on `stream`; needs no fmcw_set_taps.  Acts
+ * on the context's first device.  F = 0 is a no-op.  The call is cut into launch groups by
+ * fmcw_cfar_device's list-scratch budget. */
+int fmcw_oscfar_device(fmcw_ctx* ctx, const fmcw_oscfar_params* q, const void* d_rd, int32_t rd_dtype,
+                       int64_t F, int32_t nr, int32_t nd, int32_t* d_det_count,
+                       int32_t* d_det_range_idx, int32_t* d_det_doppler_idx, float* d_det_power,
+                       float* d_det_noise, uint8_t* d_mask, void* stream);
+
+/* Host pointers: staged, sharded over the context's devices and chunked as fmcw_cfar is
+ * (bit-identical shards and chunks); returns when the outputs are on the host. */
+int fmcw_oscfar(fmcw_ctx* ctx, const fmcw_oscfar_params* q, const void* rd, int32_t rd_dtype, int64_t F,
+                int32_t nr, int32_t nd, int32_t* det_count, int32_t* det_range_idx,
+                int32_t* det_doppler_idx, float* det_power, float* det_noise, uint8_t* mask);
 
 /* ---------------------------------------------------------------------------
  * Doppler-time (micro-Doppler) and range-time signatures of the RD map (added within ABI 4;

@@ -27,6 +27,9 @@
  *                                        fmcw_cfar_params; rd: single complex Nd x Nr x F (the C array
  *                                        [F][Nr][Nd]: permute(range_Doppler, [2 1 3])); ridx ... noise are
  *                                        max_det x F
+ *   [cnt, ridx, didx, power, noise] = fmcw_mex('oscfar', Q, rd)   -> fmcw_oscfar: 2-D ordered-statistic CFAR over
+ *                                        an RD map; Q: the fields of 'cfar' plus rank (1..N_full); rd and the
+ *                                        outputs as for 'cfar', noise holding the order statistic X_(k)
  *   [dt, rt, dt_max, rt_max] = fmcw_mex('signature', Q, rd[, center])  -> fmcw_sig: Doppler-time (micro-Doppler)
  *                                        and range-time signatures of an RD map (beyond the reference); Q: a
  *                                        struct with the fields of fmcw_sig_params; rd as for 'cfar'; center:
@@ -318,8 +321,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                       mxGetSingles(plhs[2])));
     return;
   }
-  if (!strcmp(cmd, "cfar")) {               /* [cnt, ridx, didx, power, noise] = fmcw_mex('cfar', Q, rd) */
-    if (nrhs != 3) mexErrMsgIdAndTxt("fmcw:arg", "cfar: Q, rd");
+  const int os = !strcmp(cmd, "oscfar");    /* 'oscfar': the outputs of 'cfar', Q with the field rank besides */
+  if (os || !strcmp(cmd, "cfar")) {         /* [cnt, ridx, didx, power, noise] = fmcw_mex('cfar', Q, rd) */
+    if (nrhs != 3) mexErrMsgIdAndTxt("fmcw:arg", os ? "oscfar: Q, rd" : "cfar: Q, rd");
     const mxArray* s = prhs[1];
     const mxArray* rd = prhs[2];
     if (!mxIsStruct(s)) mexErrMsgIdAndTxt("fmcw:arg", "Q must be a struct");
@@ -338,15 +342,22 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     const mwSize* dims = mxGetDimensions(rd);
     const int64_t F = mxGetNumberOfDimensions(rd) >= 3 ? (int64_t)dims[2] : 1;
     const int32_t nd = (int32_t)dims[0], nr = (int32_t)dims[1];
-    check(fmcw_cfar_check(&q, nr, nd, NULL));   /* before max_det sizes the outputs */
+    fmcw_oscfar_params qo;
+    qo.win = q;
+    qo.rank = os ? (int32_t)field(s, "rank") : 1;
+    check(os ? fmcw_oscfar_check(&qo, nr, nd, NULL) : fmcw_cfar_check(&q, nr, nd, NULL));   /* before max_det sizes the outputs */
     const mwSize K = (mwSize)q.max_det;
     plhs[0] = mxCreateNumericMatrix(1, F, mxINT32_CLASS, mxREAL);    /* detections found per frame */
     plhs[1] = mxCreateNumericMatrix(K, F, mxINT32_CLASS, mxREAL);    /* range index, 1-based, 0 = unused */
     plhs[2] = mxCreateNumericMatrix(K, F, mxINT32_CLASS, mxREAL);    /* Doppler index */
     plhs[3] = mxCreateNumericMatrix(K, F, mxSINGLE_CLASS, mxREAL);   /* |D|^2 of the cell */
-    plhs[4] = mxCreateNumericMatrix(K, F, mxSINGLE_CLASS, mxREAL);   /* noise estimate S / N */
-    check(fmcw_cfar(g_ctx, &q, mxGetComplexSingles(rd), FMCW_C64, F, nr, nd, mxGetInt32s(plhs[0]), mxGetInt32s(plhs[1]),
-                    mxGetInt32s(plhs[2]), mxGetSingles(plhs[3]), mxGetSingles(plhs[4]), NULL));
+    plhs[4] = mxCreateNumericMatrix(K, F, mxSINGLE_CLASS, mxREAL);   /* noise estimate S / N ('oscfar': X_(k)) */
+    if (os)
+      check(fmcw_oscfar(g_ctx, &qo, mxGetComplexSingles(rd), FMCW_C64, F, nr, nd, mxGetInt32s(plhs[0]),
+                        mxGetInt32s(plhs[1]), mxGetInt32s(plhs[2]), mxGetSingles(plhs[3]), mxGetSingles(plhs[4]), NULL));
+    else
+      check(fmcw_cfar(g_ctx, &q, mxGetComplexSingles(rd), FMCW_C64, F, nr, nd, mxGetInt32s(plhs[0]), mxGetInt32s(plhs[1]),
+                      mxGetInt32s(plhs[2]), mxGetSingles(plhs[3]), mxGetSingles(plhs[4]), NULL));
     return;
   }
   if (!strcmp(cmd, "signature")) {          /* [dt, rt, dt_max, rt_max] = fmcw_mex('signature', Q, rd[, center]) */
