@@ -127,7 +127,7 @@ inline void shard(int64_t total, int g, int world, int64_t& f0, int64_t& n) {
   n = base + (g < rem ? 1 : 0);
 }
 
-constexpr int kStages = 17;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar, 11 cluster, 12 track, 13 mti, 14 aoa, 15 beam, 16 oscfar
+constexpr int kStages = 18;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar, 11 cluster, 12 track, 13 mti, 14 aoa, 15 beam, 16 oscfar, 17 ra
 
 }  // namespace fmcw
 
@@ -264,6 +264,9 @@ struct fmcw_ctx {
   DevBuf mt_rd, mt_bg, mt_seen;
   // fmcw_beam (host pointers): the chunk's frames of every channel and of every output on the device
   DevBuf bm_rd, bm_out;
+  // fmcw_ra (host pointers): the chunk's frames of every channel, its covariances and its spectra, and the
+  // weight table with the running maximum on the device
+  DevBuf ra_rd, ra_cov, ra_out, ra_w;
   int64_t chunk_frames = 0;
   int64_t last_coarse_tiles = -1;     // tiles the last coarse-to-fine max(P) evaluated in full (diagnostics)
   int pipe_mode = FMCW_PIPE_AUTO;

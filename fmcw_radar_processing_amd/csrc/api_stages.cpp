@@ -1,6 +1,6 @@
 // api_stages.cpp -- the RD-map stages of the libfmcw C-ABI (include/fmcw.h): 2-D CA-CFAR and OS-CFAR,
 // Doppler-time / range-time signatures, clustering, angle of arrival, tracking, the MTI clutter
-// filter and the combination of the receive channels' maps into beams.
+// filter, the combination of the receive channels' maps into beams and the range-angle maps.
 // Every stage has a host-only fmcw_*_check, a device-pointer entry and a host-pointer entry that
 // shards over the context's devices and walks its shard in chunks; the two entries share the
 // stage's *_entry check.  The rules every stage states alike take the stage's message prefix.
@@ -1081,32 +1081,35 @@ int fmcw_beam_check(const fmcw_beam_params* q, int32_t nr, int32_t nd) {
   return FMCW_OK;
 }
 
-int fmcw_beam_steer(int32_t n_chan, int32_t n_beam, float spacing, const float* sin_theta, const float* cal,
-                    const float* taper, int32_t normalize, fmcw_beam_params* q) {
+// The weights of n_dir look directions of a uniform line of n_chan elements, flat [n_dir][n_chan][2]:
+// what fmcw_beam_steer and fmcw_ra_steer both are (one formula, one rounding, one set of argument
+// rules; `stage` prefixes the messages, `count` names the number of directions, at most max_dir).
+static int steer_table(const std::string& stage, const char* count, int max_dir, int32_t n_chan, int32_t n_dir, float spacing,
+                       const float* sin_theta, const float* cal, const float* taper, int32_t normalize, std::vector<float>& w) {
 #pragma clang fp contract(off)
-  if (!q) return fail(FMCW_E_ARG, "beam params is NULL");
-  if (n_chan < 2 || n_chan > fmcw::kBeamMax) return fail(FMCW_E_ARG, "beam: n_chan must be in [2, 8]");
-  if (n_beam < 1 || n_beam > fmcw::kBeamMax) return fail(FMCW_E_ARG, "beam: n_beam must be in [1, 8]");
+  if (n_chan < 2 || n_chan > fmcw::kBeamMax) return fail(FMCW_E_ARG, stage + ": n_chan must be in [2, 8]");
+  if (n_dir < 1 || n_dir > max_dir)
+    return fail(FMCW_E_ARG, stage + ": " + count + " must be in [1, " + std::to_string(max_dir) + "]");
   if (!std::isfinite(spacing) || !(std::fabs(spacing) >= 0.01f && std::fabs(spacing) <= 16.f))
-    return fail(FMCW_E_ARG, "beam: spacing must be finite with 0.01 <= |spacing| <= 16");
-  if (!sin_theta) return fail(FMCW_E_ARG, "beam: sin_theta is NULL");
-  for (int b = 0; b < n_beam; ++b)
-    if (!(sin_theta[b] >= -1.f && sin_theta[b] <= 1.f)) return fail(FMCW_E_ARG, "beam: every sin_theta must be in [-1, 1]");
+    return fail(FMCW_E_ARG, stage + ": spacing must be finite with 0.01 <= |spacing| <= 16");
+  if (!sin_theta) return fail(FMCW_E_ARG, stage + ": sin_theta is NULL");
+  for (int b = 0; b < n_dir; ++b)
+    if (!(sin_theta[b] >= -1.f && sin_theta[b] <= 1.f)) return fail(FMCW_E_ARG, stage + ": every sin_theta must be in [-1, 1]");
   if (cal)
     for (int i = 0; i < 2 * n_chan; ++i)
-      if (!std::isfinite(cal[i])) return fail(FMCW_E_ARG, "beam: cal must be finite");
+      if (!std::isfinite(cal[i])) return fail(FMCW_E_ARG, stage + ": cal must be finite");
   double norm = normalize ? (double)n_chan : 1.0;
   if (taper) {
     double sum = 0.0;
     for (int a = 0; a < n_chan; ++a) {
-      if (!std::isfinite(taper[a])) return fail(FMCW_E_ARG, "beam: taper must be finite");
+      if (!std::isfinite(taper[a])) return fail(FMCW_E_ARG, stage + ": taper must be finite");
       sum = sum + (double)taper[a];
     }
-    if (normalize && sum == 0.0) return fail(FMCW_E_ARG, "beam: normalize needs a taper whose sum is not 0");
+    if (normalize && sum == 0.0) return fail(FMCW_E_ARG, stage + ": normalize needs a taper whose sum is not 0");
     if (normalize) norm = sum;
   }
-  float w[fmcw::kBeamMax][fmcw::kBeamMax][2] = {};
-  for (int b = 0; b < n_beam; ++b)
+  w.assign((size_t)n_dir * n_chan * 2, 0.f);
+  for (int b = 0; b < n_dir; ++b)
     for (int a = 0; a < n_chan; ++a) {
       // the phase -2 pi spacing a sin(theta) in turns, reduced to [-1/2, 1/2], then split into k whole
       // quarter turns and a rest f in [-1/2, 1/2] of a quarter turn: f = 0 gives exactly 1 and 0
@@ -1125,10 +1128,24 @@ int fmcw_beam_steer(int32_t n_chan, int32_t n_beam, float spacing, const float* 
       }
       const double g = (taper ? (double)taper[a] : 1.0) / norm;
       const double gr = (cal ? (double)cal[2 * a] : 1.0) * g, gi = (cal ? (double)cal[2 * a + 1] : 0.0) * g;
-      w[b][a][0] = (float)(gr * er - gi * ei);
-      w[b][a][1] = (float)(gr * ei + gi * er);
-      if (!std::isfinite(w[b][a][0]) || !std::isfinite(w[b][a][1]))
-        return fail(FMCW_E_ARG, "beam: a weight does not fit float32");
+      float* const o = &w[((size_t)b * n_chan + a) * 2];
+      o[0] = (float)(gr * er - gi * ei);
+      o[1] = (float)(gr * ei + gi * er);
+      if (!std::isfinite(o[0]) || !std::isfinite(o[1])) return fail(FMCW_E_ARG, stage + ": a weight does not fit float32");
+    }
+  return FMCW_OK;
+}
+
+int fmcw_beam_steer(int32_t n_chan, int32_t n_beam, float spacing, const float* sin_theta, const float* cal,
+                    const float* taper, int32_t normalize, fmcw_beam_params* q) {
+  if (!q) return fail(FMCW_E_ARG, "beam params is NULL");
+  std::vector<float> t;
+  CHK(steer_table("beam", "n_beam", fmcw::kBeamMax, n_chan, n_beam, spacing, sin_theta, cal, taper, normalize, t));
+  float w[fmcw::kBeamMax][fmcw::kBeamMax][2] = {};
+  for (int b = 0; b < n_beam; ++b)
+    for (int a = 0; a < n_chan; ++a) {
+      w[b][a][0] = t[((size_t)b * n_chan + a) * 2];
+      w[b][a][1] = t[((size_t)b * n_chan + a) * 2 + 1];
     }
   q->n_chan = n_chan;
   q->n_beam = n_beam;
@@ -1248,6 +1265,182 @@ int fmcw_beam(fmcw_ctx* c, const fmcw_beam_params* q, const void* const* rd_ch, 
     for (int b = 0; b < B; ++b) o0[b] = static_cast<char*>(out[b]) + (size_t)f0 * fin;
     return beam_host_one(d, q, ch0, rd_dtype, n, nr, nd, o0);
   });
+}
+
+// ---------------------------------------------------------------------------
+// Range-angle maps: the channels' spatial covariance per range row and its Bartlett / Capon
+// spectra (kernels_ra.hip)
+// ---------------------------------------------------------------------------
+// the rules of fmcw_ra_params; fmcw_ra_device has no nd to hold dc_half against
+static int ra_rules(const fmcw_ra_params* q, int32_t nr, int32_t nd, bool have_nd) {
+  if (!q) return fail(FMCW_E_ARG, "ra params is NULL");
+  CHK(check_rd_shape("ra", nr, have_nd ? nd : 4));
+  CHK(check_gate("ra", q->r_lo, q->r_hi, nr));
+  if (q->n_chan < 2 || q->n_chan > fmcw::kRaChan) return fail(FMCW_E_ARG, "ra: n_chan must be in [2, 8]");
+  if (q->n_ang < 1 || q->n_ang > fmcw::kRaAngMax) return fail(FMCW_E_ARG, "ra: n_ang must be in [1, 256]");
+  if (q->dc_half < -1) return fail(FMCW_E_ARG, "ra: dc_half must be >= -1 (-1 leaves no Doppler bin out)");
+  if (have_nd && 2 * (int64_t)q->dc_half + 1 >= nd) return fail(FMCW_E_ARG, "ra: 2 dc_half + 1 must be < nd");
+  if (q->flags & ~FMCW_RA_CAPON) return fail(FMCW_E_ARG, "ra: unknown flag bits");
+  if (!(std::isfinite(q->load) && q->load >= 0.f)) return fail(FMCW_E_ARG, "ra: load must be finite and >= 0");
+  return FMCW_OK;
+}
+
+int fmcw_ra_check(const fmcw_ra_params* q, int32_t nr, int32_t nd) { return ra_rules(q, nr, nd, true); }
+
+int fmcw_ra_steer(int32_t n_chan, int32_t n_ang, float spacing, const float* sin_theta, const float* cal, const float* taper,
+                  int32_t normalize, float* w) {
+  if (!w) return fail(FMCW_E_ARG, "ra: w is NULL");
+  std::vector<float> t;
+  CHK(steer_table("ra", "n_ang", fmcw::kRaAngMax, n_chan, n_ang, spacing, sin_theta, cal, taper, normalize, t));
+  std::memcpy(w, t.data(), t.size() * sizeof(float));
+  return FMCW_OK;
+}
+
+// what the three calls check before they look at F == 0 and the pointers
+static int ra_entry(fmcw_ctx* c, const fmcw_ra_params* q, int64_t F, int32_t nr, int32_t nd, bool have_nd) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(ra_rules(q, nr, nd, have_nd));
+  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
+  if (F > ((int64_t)1 << 40)) return fail(FMCW_E_ARG, "ra: F must be at most 2^40");
+  return FMCW_OK;
+}
+
+int fmcw_cov_device(fmcw_ctx* c, const fmcw_ra_params* q, const void* const* d_rd_ch, int32_t rd_dtype, int64_t F, int32_t nr,
+                    int32_t nd, float* d_cov, void* stream) {
+  CHK(ra_entry(c, q, F, nr, nd, true));
+  CHK(check_rd_dtype(rd_dtype));
+  if (F == 0) return FMCW_OK;
+  if (!d_rd_ch || !d_cov) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const int A = q->n_chan;
+  for (int a = 0; a < A; ++a)
+    if (!d_rd_ch[a]) return fail(FMCW_E_ARG, "required pointer is NULL");
+  for (int a = 0; a < A; ++a)
+    if (reinterpret_cast<uintptr_t>(d_rd_ch[a]) & 15) return fail(FMCW_E_ARG, "ra: every channel's d_rd must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_cov) & 15) return fail(FMCW_E_ARG, "ra: d_cov must be 16-byte aligned");
+  CHK(set_device(c));
+  hipStream_t s = pick(c, stream);
+  fmcw::CovArgs a{};
+  a.A = A; a.NR = nr; a.ND = nd;
+  a.h = rd_dtype == FMCW_C32H;
+  a.scale2 = a.h ? ((float)nr * (float)nd) * ((float)nr * (float)nd) : 1.f;
+  gate_rows(q->r_lo, q->r_hi, nr, a.g0, a.g1);
+  a.dc = q->dc_half;
+  a.rpw = fmcw::cov_rows_per_wave(nd, a.h);
+  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
+  const size_t T = (size_t)A * (A + 1) / 2;
+  // at most kRaRowsMax rows per launch (the results do not depend on the cut)
+  const int64_t Fc = fmcw::kRaRowsMax / nr;
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    a.rows = std::min(Fc, F - f0) * nr;
+    for (int ch = 0; ch < A; ++ch) a.rd[ch] = static_cast<const char*>(d_rd_ch[ch]) + (size_t)f0 * fin;
+    a.cov = d_cov + (size_t)f0 * nr * T * 2;
+    StageTimer tm(c, 17, s);
+    HIPCHK(fmcw::launch_cov(a, s));
+    tm.done();
+  }
+  return FMCW_OK;
+}
+
+int fmcw_ra_device(fmcw_ctx* c, const fmcw_ra_params* q, const float* d_cov, int64_t F, int32_t nr, const float* d_w,
+                   float* d_ra, float* d_ra_max, void* stream) {
+  CHK(ra_entry(c, q, F, nr, 0, false));
+  if (F == 0) return FMCW_OK;
+  if (!d_cov || !d_w || !d_ra) return fail(FMCW_E_ARG, "required pointer is NULL");
+  if ((reinterpret_cast<uintptr_t>(d_cov) | reinterpret_cast<uintptr_t>(d_w) | reinterpret_cast<uintptr_t>(d_ra)) & 15)
+    return fail(FMCW_E_ARG, "ra: d_cov, d_w and d_ra must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_ra_max) & 3) return fail(FMCW_E_ARG, "ra: d_ra_max must be 4-byte aligned");
+  CHK(set_device(c));
+  hipStream_t s = pick(c, stream);
+  fmcw::RaArgs a{};
+  a.A = q->n_chan; a.NR = nr; a.n_ang = q->n_ang;
+  gate_rows(q->r_lo, q->r_hi, nr, a.g0, a.g1);
+  a.capon = (q->flags & FMCW_RA_CAPON) ? 1 : 0;
+  a.load = q->load;
+  a.w = d_w;
+  a.ra_max = d_ra_max;
+  const size_t T = (size_t)a.A * (a.A + 1) / 2;
+  const int64_t Fc = fmcw::kRaRowsMax / nr;
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    a.rows = std::min(Fc, F - f0) * nr;
+    a.cov = d_cov + (size_t)f0 * nr * T * 2;
+    a.ra = d_ra + (size_t)f0 * nr * a.n_ang;
+    StageTimer tm(c, 17, s);
+    HIPCHK(fmcw::launch_ra(a, s));
+    tm.done();
+  }
+  return FMCW_OK;
+}
+
+// One shard of fmcw_ra, chunk by chunk: the chunk's frames of every channel in, cov and ra out.
+static int ra_host_one(fmcw_ctx* c, const fmcw_ra_params* q, const char* const* rd_ch, int32_t dtype, int64_t F, int32_t nr,
+                       int32_t nd, const float* w, float* cov, float* ra, float* mx) {
+  CHK(set_device(c));
+  hipStream_t s = c->stream;
+  const int A = q->n_chan, K = q->n_ang;
+  const size_t fin = (size_t)nr * nd * esize(dtype);
+  const size_t covf = (size_t)nr * A * (A + 1), raf = (size_t)nr * K;   // floats per frame
+  const int64_t Fc = host_chunk((size_t)A * fin, F);
+  Arena ar;
+  const size_t o_w = ar.add((size_t)K * A * 8), o_mx = ar.add(4);
+  CHK(c->ra_rd.ensure((size_t)A * Fc * fin));
+  CHK(c->ra_cov.ensure((size_t)Fc * covf * 4));
+  char* const dr = c->ra_rd.as<char>();
+  const void* d_ch[fmcw::kRaChan] = {};
+  for (int ch = 0; ch < A; ++ch) d_ch[ch] = dr + (size_t)ch * Fc * fin;   // a multiple of 256 bytes apart
+  // the spectra's buffers only where the spectra are asked for
+  float* d_w = nullptr;
+  float* d_mx = nullptr;
+  if (ra) {
+    CHK(c->ra_out.ensure((size_t)Fc * raf * 4));
+    CHK(c->ra_w.ensure(ar.off));
+    d_w = reinterpret_cast<float*>(c->ra_w.as<char>() + o_w);
+    d_mx = reinterpret_cast<float*>(c->ra_w.as<char>() + o_mx);
+    HIPCHK(hipMemsetAsync(d_mx, 0, 4, s));
+    HIPCHK(hipMemcpyAsync(d_w, w, (size_t)K * A * 8, hipMemcpyHostToDevice, s));
+  }
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    const int64_t nf = std::min(Fc, F - f0);
+    for (int ch = 0; ch < A; ++ch)
+      HIPCHK(hipMemcpyAsync(dr + (size_t)ch * Fc * fin, rd_ch[ch] + (size_t)f0 * fin, (size_t)nf * fin, hipMemcpyHostToDevice, s));
+    CHK(fmcw_cov_device(c, q, d_ch, dtype, nf, nr, nd, c->ra_cov.as<float>(), s));
+    if (ra) CHK(fmcw_ra_device(c, q, c->ra_cov.as<float>(), nf, nr, d_w, c->ra_out.as<float>(), d_mx, s));
+    if (cov) HIPCHK(hipMemcpyAsync(cov + (size_t)f0 * covf, c->ra_cov.p, (size_t)nf * covf * 4, hipMemcpyDeviceToHost, s));
+    if (ra) HIPCHK(hipMemcpyAsync(ra + (size_t)f0 * raf, c->ra_out.p, (size_t)nf * raf * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));           // the chunk buffers are reused by the next chunk
+  }
+  *mx = 0.f;
+  if (ra) HIPCHK(hipMemcpyAsync(mx, d_mx, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return FMCW_OK;
+}
+
+int fmcw_ra(fmcw_ctx* c, const fmcw_ra_params* q, const void* const* rd_ch, int32_t rd_dtype, int64_t F, int32_t nr, int32_t nd,
+            const float* w, float* cov, float* ra, float* ra_max) {
+  CHK(ra_entry(c, q, F, nr, nd, true));
+  CHK(check_rd_dtype(rd_dtype));
+  if (!cov && !ra) return fail(FMCW_E_ARG, "ra: cov and ra are both NULL");
+  if (F == 0) {
+    if (ra_max) *ra_max = 0.f;
+    return FMCW_OK;
+  }
+  if (!rd_ch || (ra && !w)) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const int A = q->n_chan;
+  for (int ch = 0; ch < A; ++ch)
+    if (!rd_ch[ch]) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const size_t fin = (size_t)nr * nd * esize(rd_dtype);
+  const int64_t covf = (int64_t)nr * A * (A + 1), raf = (int64_t)nr * q->n_ang;
+  const int world = 1 + (int)c->peers.size();
+  std::vector<float> mx((size_t)world, 0.f);
+  // frames are independent: contiguous shards, each written in place
+  CHK(over_devices(c, F, [&](fmcw_ctx* d, int g, int64_t f0, int64_t n) {
+    const char* ch0[fmcw::kRaChan] = {};
+    for (int ch = 0; ch < A; ++ch) ch0[ch] = static_cast<const char*>(rd_ch[ch]) + (size_t)f0 * fin;
+    return ra_host_one(d, q, ch0, rd_dtype, n, nr, nd, w, shifted(cov, f0 * covf), shifted(ra, f0 * raf), &mx[(size_t)g]);
+  }));
+  float gmx = 0.f;                             // a maximum of non-negative floats does not depend on order
+  for (int g = 0; g < world; ++g) gmx = std::max(gmx, mx[(size_t)g]);
+  if (ra_max) *ra_max = gmx;
+  return FMCW_OK;
 }
 
 }  // extern "C"

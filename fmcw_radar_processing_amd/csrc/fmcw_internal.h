@@ -448,6 +448,37 @@ struct BeamArgs {
 };
 hipError_t launch_beam(const BeamArgs& a, hipStream_t s);
 
+// Range-angle maps (kernels_ra.hip): k_cov (the channels' spatial covariance per range row) and
+// k_ra (the Bartlett / Capon spectrum of every row)
+constexpr int kRaChan = 8;             // channels at most
+constexpr int kRaAngMax = 256;         // look directions at most
+constexpr int64_t kRaRowsMax = (int64_t)1 << 30;   // rows (frames * NR) of one launch at most
+struct CovArgs {
+  const void* rd[kRaChan];         // channel a: the launch's frames, [rows][ND] c64 or c32h; 16-byte aligned
+  float* cov;                      // [rows][T][2], T = A (A + 1) / 2; 8-byte aligned
+  int64_t rows;                    // frames * NR of the launch
+  int A, NR, ND;
+  int h;                           // fp16 storage
+  int g0, g1;                      // gated rows, 0-based, inclusive
+  int dc;                          // dc_half, -1 = keep every Doppler bin
+  int rpw;                         // rows a wave takes one after the other where a row fills a wave-load (cov_rows_per_wave)
+  float scale2;                    // (NR * ND)^2 when h, else 1
+};
+int cov_rows_per_wave(int nd, int h);
+hipError_t launch_cov(const CovArgs& a, hipStream_t s);
+struct RaArgs {
+  const float* cov;                // [rows][T][2]
+  const float* w;                  // [n_ang][A][2]
+  float* ra;                       // [rows][n_ang]
+  float* ra_max;                   // running maximum or nullptr
+  int64_t rows;
+  int A, NR, n_ang;
+  int g0, g1;
+  int capon;
+  float load;
+};
+hipError_t launch_ra(const RaArgs& a, hipStream_t s);
+
 bool range_size_supported(int nr);
 bool doppler_size_supported(int nd);
 

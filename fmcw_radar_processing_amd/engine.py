@@ -17,8 +17,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import FMCW_C32H, FMCW_C64, STAGES, FmcwError, check
-from .params import (AoaConfig, BeamConfig, CfarConfig, ClusterConfig, FmcwConfig, MtiConfig, OsCfarConfig, SigConfig,
-                     TrackConfig)
+from .params import (AoaConfig, BeamConfig, CfarConfig, ClusterConfig, FmcwConfig, MtiConfig, OsCfarConfig, RaConfig,
+                     SigConfig, TrackConfig)
 
 
 def _ptr(a) -> ct.c_void_p:
@@ -738,6 +738,76 @@ class Engine:
         with _sided(stream) as hs:
             check(self.lib.fmcw_beam_device(self.h, ct.byref(qa), ptrs, int(rd_dtype), int(F), int(nr), int(nd), optrs,
                                             hs))
+
+    # ---- range-angle maps: covariance, Bartlett and Capon spectra (include/fmcw.h, fmcw_ra_params) ----
+    @staticmethod
+    def ra_weights(n_chan: int, sin_theta=None, spacing: float = 0.5, cal=None, taper=None, normalize: bool = True,
+                   n_ang: int = 65) -> np.ndarray:
+        """fmcw_ra_steer: complex64 [n_ang][n_chan], the weights of one look direction per entry of
+        sin_theta (default: n_ang points uniform in sin(theta) over [-1, 1]) for a uniform line of
+        n_chan elements `spacing` wavelengths apart; the arguments are those of beam_weights, for up
+        to 256 directions.  Feed the result to range_angle."""
+        if sin_theta is None:
+            sin_theta = np.linspace(-1.0, 1.0, int(n_ang)) if int(n_ang) > 1 else np.zeros(1)
+        st = np.ascontiguousarray(np.atleast_1d(sin_theta), np.float32)
+        c = None if cal is None else np.ascontiguousarray(
+            np.asarray(cal, np.complex64).reshape(-1)).view(np.float32)
+        t = None if taper is None else np.ascontiguousarray(np.asarray(taper, np.float32).reshape(-1))
+        if (c is not None and c.size != 2 * int(n_chan)) or (t is not None and t.size != int(n_chan)):
+            raise ValueError("ra_weights: cal and taper need one value per channel")
+        w = np.zeros((max(st.size, 1), max(int(n_chan), 1), 2), np.float32)
+        check(_lib.load().fmcw_ra_steer(int(n_chan), int(st.size), float(spacing), _ptr(st), _ptr(c), _ptr(t),
+                                        1 if normalize else 0, _ptr(w)))
+        return w.view(np.complex64).reshape(st.size, int(n_chan))
+
+    def range_angle(self, rds, q: RaConfig, w=None, want_cov: bool = True, want_ra: bool = True) -> tuple:
+        """(ra, cov, ra_max) from the q.n_chan RD maps `rds`, one per receive channel, each complex64
+        [F][nr][nd] or float16 [F][nr][nd][2] holding D / (nr nd), all of one dtype and shape.  w:
+        complex [q.n_ang][q.n_chan] of ra_weights (needed with want_ra).  Host arrays, frames sharded
+        over the context's devices.  ra float32 [F][nr][q.n_ang] (None without want_ra), cov float32
+        [F][nr][T][2], T = n_chan (n_chan + 1) / 2 (None without want_cov), ra_max the largest value
+        of ra as float (0 without want_ra)."""
+        chans = [_host_rd(rd, "F") for rd in rds]
+        A, K = int(q.n_chan), int(q.n_ang)
+        if len(chans) != A:
+            raise ValueError("ra: rds must hold q.n_chan maps")
+        dt = chans[0][1]
+        if any(c[1] != dt or c[0].shape != chans[0][0].shape for c in chans):
+            raise ValueError("ra: the channels must share one dtype and shape")
+        F, nr, nd = chans[0][0].shape[:3]
+        wf = None
+        if want_ra:
+            if w is None:
+                raise ValueError("ra: the spectra need a weight table (Engine.ra_weights)")
+            wf = np.ascontiguousarray(np.asarray(w).astype(np.complex64))
+            if wf.shape != (K, A):
+                raise ValueError("ra: w must be [q.n_ang][q.n_chan] complex")
+        cov = np.empty((F, nr, A * (A + 1) // 2, 2), np.float32) if want_cov else None
+        ra = np.empty((F, nr, K), np.float32) if want_ra else None
+        mx = ct.c_float(0.0)
+        qa = q.abi()
+        ptrs = (ct.c_void_p * max(len(chans), 1))(*[c[0].ctypes.data for c in chans])
+        check(self.lib.fmcw_ra(self.h, ct.byref(qa), ptrs, dt, F, nr, nd, _ptr(wf), _ptr(cov), _ptr(ra), ct.byref(mx)))
+        return ra, cov, float(mx.value)
+
+    def cov_device(self, q: RaConfig, d_rds, rd_dtype: int, F: int, nr: int, nd: int, d_cov, stream=None) -> None:
+        """fmcw_cov_device: d_rds the q.n_chan device RD maps [F][nr][nd] of rd_dtype (separate
+        allocations or slices of one, each 16-byte aligned); d_cov float32 [F][nr][T][2].  q: a
+        RaConfig, or the C struct _lib.RaParams itself.  Asynchronous on `stream`."""
+        qa = q.abi() if hasattr(q, "abi") else q
+        ptrs = (ct.c_void_p * max(len(d_rds), 1))(*[_ptr(d).value or 0 for d in d_rds])
+        with _sided(stream) as hs:
+            check(self.lib.fmcw_cov_device(self.h, ct.byref(qa), ptrs, int(rd_dtype), int(F), int(nr), int(nd),
+                                           _ptr(d_cov), hs))
+
+    def range_angle_device(self, q: RaConfig, d_cov, F: int, nr: int, d_w, d_ra, d_ra_max=None, stream=None) -> None:
+        """fmcw_ra_device: d_cov float32 [F][nr][T][2] (of cov_device, or the caller's own), d_w
+        float32 [q.n_ang][q.n_chan][2], d_ra float32 [F][nr][q.n_ang]; d_ra_max one float32 zeroed by
+        the caller, or None.  signature_db_device turns d_ra into dB.  Asynchronous on `stream`."""
+        qa = q.abi() if hasattr(q, "abi") else q
+        with _sided(stream) as hs:
+            check(self.lib.fmcw_ra_device(self.h, ct.byref(qa), _ptr(d_cov), int(F), int(nr), _ptr(d_w), _ptr(d_ra),
+                                          _ptr(d_ra_max), hs))
 
     # ---- timing -----------------------------------------------------------------
     def timing(self, level: int) -> None:

@@ -12,8 +12,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import windows
-from ._lib import (FMCW_BEAM_NCI, FMCW_CFAR_LOCAL_MAX, FMCW_MTI_FREEZE, FMCW_MTI_RAMP, FMCW_SIG_DB, AoaParams,
-                   BeamParams, CfarParams, ClusterParams, MtiParams, OsCfarParams, Params, SigParams, TrackParams)
+from ._lib import (FMCW_BEAM_NCI, FMCW_CFAR_LOCAL_MAX, FMCW_MTI_FREEZE, FMCW_MTI_RAMP, FMCW_RA_CAPON, FMCW_SIG_DB, AoaParams,
+                   BeamParams, CfarParams, ClusterParams, MtiParams, OsCfarParams, Params, RaParams, SigParams, TrackParams)
 
 C0 = 3e8  # radar_processing.m:67
 
@@ -600,3 +600,48 @@ class BeamConfig:
             raise ValueError("beam: FMCW_BEAM_NCI needs n_beam == 1")
         if not np.isfinite(self.weights_f32()).all():
             raise ValueError("beam: the weights must be finite")
+
+
+@dataclass
+class RaConfig:
+    """fmcw_ra_params (include/fmcw.h): range-angle maps from n_chan receive channels' RD maps.  Per
+    range row the channels' spatial covariance over the Doppler bins kept (dc_half leaves the bins
+    |d - nd/2| <= dc_half out, -1: none), then its angular power spectrum over n_ang look directions
+    (a weight table of Engine.ra_weights): Bartlett, or with capon the Capon / MVDR spectrum under
+    the diagonal loading `load` (relative to the mean diagonal).  The gate r_lo..r_hi is 1-based and
+    inclusive, (0, 0) = every row; rows outside it are zero."""
+    n_chan: int
+    n_ang: int
+    r_lo: int = 0
+    r_hi: int = 0
+    dc_half: int = 0
+    capon: bool = False
+    load: float = 1e-3
+
+    def abi(self) -> RaParams:
+        return RaParams(int(self.n_chan), int(self.n_ang), int(self.r_lo), int(self.r_hi), int(self.dc_half),
+                        FMCW_RA_CAPON if self.capon else 0, self.load)
+
+    def validate(self, nr: int, nd: int) -> None:
+        """The rules of fmcw_ra_check, on the float32 value the C struct carries; ValueError naming
+        the first one violated."""
+        if nr < 16 or nr > 2048 or nr & (nr - 1):
+            raise ValueError("ra: nr must be a power of two in [16, 2048]")
+        if nd < 4 or nd > 1024 or nd & (nd - 1):
+            raise ValueError("ra: nd must be a power of two in [4, 1024]")
+        if self.r_lo > self.r_hi:
+            raise ValueError("ra: r_lo > r_hi")
+        if (self.r_lo, self.r_hi) != (0, 0) and (self.r_lo < 1 or self.r_hi > nr):
+            raise ValueError("ra: the gate r_lo..r_hi must lie in 1..nr (or be 0, 0 for all rows)")
+        if not 2 <= self.n_chan <= 8:
+            raise ValueError("ra: n_chan must be in [2, 8]")
+        if not 1 <= self.n_ang <= 256:
+            raise ValueError("ra: n_ang must be in [1, 256]")
+        if self.dc_half < -1:
+            raise ValueError("ra: dc_half must be >= -1 (-1 leaves no Doppler bin out)")
+        if 2 * self.dc_half + 1 >= nd:
+            raise ValueError("ra: 2 dc_half + 1 must be < nd")
+        with np.errstate(over="ignore"):
+            load = np.float32(self.load)
+        if not (np.isfinite(load) and load >= 0):
+            raise ValueError("ra: load must be finite and >= 0")

@@ -58,7 +58,9 @@ extern "C" {
  *    fmcw_beam), the struct fmcw_beam_params and timing stage 15, added within ABI 4 in the same way
  *    + the ordered-statistic CFAR entry points (fmcw_oscfar_check, fmcw_oscfar_alpha,
  *    fmcw_oscfar_device, fmcw_oscfar), the struct fmcw_oscfar_params and timing stage 16, added
- *    within ABI 4 in the same way */
+ *    within ABI 4 in the same way
+ *    + the range-angle entry points (fmcw_ra_check, fmcw_ra_steer, fmcw_cov_device, fmcw_ra_device,
+ *    fmcw_ra), the struct fmcw_ra_params and timing stage 17, added within ABI 4 in the same way */
 #define FMCW_ABI_VERSION 4
 
 typedef enum fmcw_status {
@@ -292,7 +294,8 @@ int fmcw_synth_device(fmcw_ctx* ctx, const fmcw_params* p, int64_t frame0, int64
  *        13 mti (one pair per fmcw_mti_device call's k_mti + k_mti_seen launches), 14 aoa (one pair
  *        per k_aoa launch of fmcw_aoa_device), 15 beam (one pair per k_beam launch of
  *        fmcw_beam_device), 16 oscfar (one pair per k_oscfar + k_cfar_gather + k_oscfar_select
- *        launch group of fmcw_oscfar_device).
+ *        launch group of fmcw_oscfar_device), 17 ra (one pair per k_cov launch of fmcw_cov_device
+ *        and one per k_ra launch of fmcw_ra_device).
  *        fmcw_timing_read synchronises. */
 int fmcw_timing_enable(fmcw_ctx* ctx, int32_t enable);
 int fmcw_timing_read(fmcw_ctx* ctx, int32_t stage, double* total_ms, int64_t* launches);
@@ -979,6 +982,109 @@ int fmcw_beam_device(fmcw_ctx* ctx, const fmcw_beam_params* q, const void* const
  * returns when the outputs are on the host. */
 int fmcw_beam(fmcw_ctx* ctx, const fmcw_beam_params* q, const void* const* rd_ch, int32_t rd_dtype, int64_t F,
               int32_t nr, int32_t nd, void* const* out);
+
+/* ---------------------------------------------------------------------------
+ * Range-angle maps: the spatial covariance of the receive channels per range row, and the Bartlett
+ * and Capon (MVDR) angular power spectra taken from it (added within ABI 4; beyond the reference).
+ * fmcw_aoa* gives one angle per detection and fmcw_beam* at most eight fixed beams; this stage gives
+ * an angular spectrum for every range row on a grid of up to 256 look directions, and the covariance
+ * itself, which is the input of any subspace method.  Indices below are 0-based; the gate is 1-based
+ * as everywhere else.
+ *   Input: A channel maps rd[a], A in 2..8, each [F][nr][nd], all FMCW_C64 or all FMCW_C32H, given as
+ *     a host array of A pointers exactly as fmcw_beam takes them (device call: each 16-byte aligned);
+ *     nr, nd within CFAR's limits.
+ *   Stage 1, covariance.  For every frame f and every gated row r,
+ *       R_ab = sum over d of x_a[r][d] conj(x_b[r][d])
+ *     over the Doppler bins that are not left out: a bin is left out when circular
+ *     |d - nd/2| <= dc_half, exactly fmcw_sig's rule (dc_half = -1 keeps every bin); N = bins kept.
+ *     cov [F][nr][T][2] float32, T = A (A + 1) / 2: the packed upper triangle, entry (a, b), a <= b,
+ *     at index a A - a (a - 1) / 2 + (b - a), each (re, im); a diagonal entry has im = +0.  Rows
+ *     outside the gate r_lo..r_hi are all zero (0, 0: all rows).  fp16 storage: the stored values
+ *     are widened exactly and the written sums are multiplied by ((float)nr (float)nd)^2, an exact
+ *     power of two (the scale of fmcw_sig and fmcw_aoa).
+ *     Accuracy: the order of the sum and the contraction of multiply-adds are the kernel's own.
+ *     Every component of every entry is within (N + 8) 2^-24 sqrt(R_aa R_bb) of the exact sum of
+ *     the stored values: a product term has at most 3 roundings of relative size 2^-24 against
+ *     |x_a| |x_b|, a sum of N terms in any order adds (N - 1) 2^-24 sum |x_a| |x_b|, and
+ *     sum_d |x_a| |x_b| <= sqrt(R_aa R_bb) (Cauchy-Schwarz); the 8 is fmcw_sig's margin.  For a
+ *     diagonal entry, a sum of non-negative terms, this is fmcw_sig's relative bound.
+ *     Determinism: the order is fixed by (A, nr, nd, dtype, dc_half, gate) alone and no float atomics
+ *     are used, so the bytes do not depend on the call, on F, on sharding or on chunking.
+ *   Stage 2, spectra, from the float32 cov bytes and a weight table w [n_ang][A][2], n_ang in 1..256:
+ *     w[k] holds the beam weights of look direction k in fmcw_beam_steer's convention
+ *     (w = conj(steering) / norm).  ra [F][nr][n_ang] float32, a power in the units of cov; rows
+ *     outside the gate are zero.  Everything is float32, every operation rounded on its own in the
+ *     order written (no fused multiply-add), divides and square roots correctly rounded: every
+ *     output byte equals a float32 numpy evaluation of the same steps on the same cov bytes.
+ *     Bartlett (flags 0): acc = 0; for a = 0..A-1, for b = a..A-1:
+ *       c.re = wa.re wb.re + wa.im wb.im;  c.im = wa.im wb.re - wa.re wb.im;
+ *       t = c.re R_ab.re - c.im R_ab.im;   acc = acc + t when a == b, else acc = acc + (t + t).
+ *       ra = acc.  This is sum_d |sum_a w_a x_a|^2: the power of fmcw_beam's beam k summed over the
+ *       kept Doppler bins.
+ *     Capon (FMCW_RA_CAPON), once per row:
+ *       tr = sum_a R_aa.re in ascending a (from 0);  delta = load (tr / (float)A).
+ *       The Cholesky factor L (lower triangular, real diagonal) of M, M_ii = R_ii.re + delta and,
+ *       for i > j, M_ij = (R_ji.re, -R_ji.im): for i = 0..A-1, for j = 0..i: s = M_ij; for
+ *       k = 0..j-1: s.re -= (Lik.re Ljk.re + Lik.im Ljk.im), s.im -= (Lik.im Ljk.re - Lik.re Ljk.im);
+ *       i == j: L_ii = sqrtf(s.re), and the row is DEGENERATE unless s.re > 0 and s.re is finite;
+ *       i > j: L_ij = (s.re / L_jj, s.im / L_jj).
+ *       Per direction: u_a = (w_a.re, -w_a.im); q = 0, e = 0; in ascending a: s = u_a; for
+ *       b = 0..a-1: s.re -= (Lab.re yb.re - Lab.im yb.im), s.im -= (Lab.re yb.im + Lab.im yb.re);
+ *       y_a = (s.re / L_aa, s.im / L_aa); q += (y_a.re^2 + y_a.im^2); e += (u_a.re^2 + u_a.im^2).
+ *       ra = (e e) / q; ra = 0 for a degenerate row or q == 0.
+ *       With w = conj(a) / A this is 1 / (a^H M^-1 a), the usual MVDR power, on the scale of the
+ *       Bartlett value: both estimate a lone source's summed power.
+ *     d_ra_max: an optional running maximum of everything written to ra, raised as an integer
+ *     atomic maximum on the float's bits as fmcw_sig does (so a negative value, which rounding can
+ *     leave in a Bartlett null, never raises it); the caller zeroes it first.  fmcw_sig_db_device
+ *     turns ra into dB.
+ *   A non-finite stored value or weight makes the outputs of the rows that hold it unspecified; it
+ *   touches nothing else and nothing out of bounds.
+ *   Parameters: n_chan = A in 2..8; n_ang in 1..256; r_lo, r_hi as fmcw_cfar_params; dc_half >= -1
+ *     with 2 dc_half + 1 < nd; flags 0 or FMCW_RA_CAPON (an unknown bit is FMCW_E_ARG); load finite
+ *     and >= 0, used only by Capon.
+ *   Measured times and the copy-time yardsticks: DESIGN.md 4.12, profiles/ra_bench.json.
+ * ------------------------------------------------------------------------- */
+enum { FMCW_RA_CAPON = 1 };
+typedef struct fmcw_ra_params {
+  int32_t n_chan;          /* A, 2..8 */
+  int32_t n_ang;           /* look directions, 1..256 */
+  int32_t r_lo, r_hi;      /* range gate, 1-based inclusive; 0, 0: all rows */
+  int32_t dc_half;         /* Doppler bins |d - nd/2| <= dc_half (circular) are left out; -1: none */
+  int32_t flags;           /* 0 (Bartlett) or FMCW_RA_CAPON */
+  float   load;            /* Capon's diagonal loading, relative to the mean diagonal; >= 0 */
+} fmcw_ra_params;
+
+/* Host only, no context: FMCW_E_ARG (with a message) for any violation of the constraints. */
+int fmcw_ra_check(const fmcw_ra_params* q, int32_t nr, int32_t nd);
+
+/* Host only, no context: the weights of n_ang look directions, w [n_ang][n_chan][2] flat.  The
+ * formula, the argument rules and the rounding are fmcw_beam_steer's (one function forms both):
+ * direction k of this table equals beam k % 8 of fmcw_beam_steer over sin_theta[8 (k / 8) ..].
+ * FMCW_E_ARG (with a message, w untouched) for any violated constraint. */
+int fmcw_ra_steer(int32_t n_chan, int32_t n_ang, float spacing, const float* sin_theta, const float* cal,
+                  const float* taper, int32_t normalize, float* w);
+
+/* Stage 1 on device pointers (d_rd_ch[a] device pointers, each 16-byte aligned, as is d_cov; the
+ * array and *q are read on the host; d_cov must not overlap a map), asynchronous on `stream`; needs
+ * no fmcw_set_taps.  Acts on the context's first device.  F = 0 is a no-op.  FMCW_E_ARG is returned
+ * before any launch: d_cov is then untouched.  n_ang, flags and load are checked but not used. */
+int fmcw_cov_device(fmcw_ctx* ctx, const fmcw_ra_params* q, const void* const* d_rd_ch, int32_t rd_dtype,
+                    int64_t F, int32_t nr, int32_t nd, float* d_cov, void* stream);
+
+/* Stage 2 on device pointers: d_cov [F][nr][T][2] is what fmcw_cov_device wrote, or a caller's own
+ * covariance (the imaginary part of a diagonal entry is not read); d_w [n_ang][n_chan][2]; d_ra
+ * [F][nr][n_ang]; all three 16-byte aligned; d_ra_max one float or NULL.  dc_half is checked
+ * against -1 only (the call has no nd).  The rest as fmcw_cov_device. */
+int fmcw_ra_device(fmcw_ctx* ctx, const fmcw_ra_params* q, const float* d_cov, int64_t F, int32_t nr,
+                   const float* d_w, float* d_ra, float* d_ra_max, void* stream);
+
+/* Host pointers (no alignment asked for): both stages, staged (all A channels of a chunk), frames
+ * sharded over the context's devices and chunked as fmcw_beam is (bit-identical shards and chunks);
+ * returns when the outputs are on the host.  cov or ra may be NULL, not both; w may be NULL without
+ * ra; *ra_max (may be NULL) is the maximum over all shards, 0 without ra. */
+int fmcw_ra(fmcw_ctx* ctx, const fmcw_ra_params* q, const void* const* rd_ch, int32_t rd_dtype, int64_t F,
+            int32_t nr, int32_t nd, const float* w, float* cov, float* ra, float* ra_max);
 
 /* ---------------------------------------------------------------------------
  * spectrogram.png, replacing radar_processing.m:331-348:

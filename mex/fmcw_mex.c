@@ -90,6 +90,18 @@
  *                                        one beam per entry of sin_theta for a uniform line, in the sign convention
  *                                        of 'aoa'; cal: 2 A doubles (re, im per plane) or [], taper: A doubles or [],
  *                                        normalize: 0 / 1 (default 1); w is (2*A) x B, double, the layout of Q.w
+ *   [ra, cov, ra_max] = fmcw_mex('ra', Q, rd4, w)                 -> fmcw_ra: range-angle maps (beyond the reference): the
+ *                                        receive planes' spatial covariance per range row and its Bartlett or, with
+ *                                        FMCW_RA_CAPON in Q.flags, Capon spectrum over the look directions of w; Q: a
+ *                                        struct with the fields r_lo, r_hi, dc_half, flags, load; rd4 as for 'aoa',
+ *                                        single complex Nd x Nr x F x A; w: a real double array of 2 x A x K values (re,
+ *                                        im; plane; direction), e.g. what 'ra_steer' returns; ra is K x (Nr*F) single
+ *                                        (a power; reshape(ra, K, Nr, F)), cov (2*T) x (Nr*F) single with T =
+ *                                        A (A + 1) / 2 (reshape(cov, 2, T, Nr, F): the packed upper triangle, re and
+ *                                        im), ra_max a double
+ *   w = fmcw_mex('ra_steer', n_chan, spacing, sin_theta[, cal, taper, normalize])
+ *                                                                 -> fmcw_ra_steer (needs no context): 'beam_steer' for up
+ *                                        to 256 look directions; w is (2*A) x K, double
  *   fmcw_mex('close')                                            -> fmcw_ctx_destroy
  *
  * P is a struct with the fields of fmcw_params (nts, pn, nr, nd, max_targets,
@@ -254,6 +266,33 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     plhs[0] = mxCreateDoubleMatrix((mwSize)(2 * A), B, mxREAL);
     for (mwSize b = 0; b < B; ++b)
       for (int i = 0; i < 2 * A; ++i) mxGetDoubles(plhs[0])[b * (mwSize)(2 * A) + i] = q.w[b][i / 2][i % 2];
+    return;
+  }
+  if (!strcmp(cmd, "ra_steer")) {           /* w = fmcw_mex('ra_steer', n_chan, spacing, sin_theta[, cal, taper, normalize]): needs no context */
+    if (nrhs < 4 || nrhs > 7) mexErrMsgIdAndTxt("fmcw:arg", "ra_steer: n_chan, spacing, sin_theta[, cal, taper, normalize]");
+    const int32_t A = (int32_t)mxGetScalar(prhs[1]);
+    const mwSize K = mxGetNumberOfElements(prhs[3]);
+    if (A < 2 || A > 8 || K < 1 || K > 256 || !mxIsDouble(prhs[3]) || mxIsComplex(prhs[3]))
+      mexErrMsgIdAndTxt("fmcw:arg", "ra_steer: n_chan in 2..8 and sin_theta a real double vector of 1..256 values");
+    float st[256], cal[16], taper[8], wf[256 * 8 * 2];
+    const float* pc = NULL;
+    const float* pt = NULL;
+    for (mwSize k = 0; k < K; ++k) st[k] = (float)mxGetDoubles(prhs[3])[k];
+    if (nrhs > 4 && mxGetNumberOfElements(prhs[4]) > 0) {
+      if (!mxIsDouble(prhs[4]) || mxIsComplex(prhs[4]) || mxGetNumberOfElements(prhs[4]) != (mwSize)(2 * A))
+        mexErrMsgIdAndTxt("fmcw:arg", "ra_steer: cal must be a real double array of 2 A values (re, im per plane)");
+      for (int i = 0; i < 2 * A; ++i) cal[i] = (float)mxGetDoubles(prhs[4])[i];
+      pc = cal;
+    }
+    if (nrhs > 5 && mxGetNumberOfElements(prhs[5]) > 0) {
+      if (!mxIsDouble(prhs[5]) || mxIsComplex(prhs[5]) || mxGetNumberOfElements(prhs[5]) != (mwSize)A)
+        mexErrMsgIdAndTxt("fmcw:arg", "ra_steer: taper must be a real double array of A values");
+      for (int i = 0; i < A; ++i) taper[i] = (float)mxGetDoubles(prhs[5])[i];
+      pt = taper;
+    }
+    check(fmcw_ra_steer(A, (int32_t)K, (float)mxGetScalar(prhs[2]), st, pc, pt, nrhs > 6 ? mxGetScalar(prhs[6]) != 0 : 1, wf));
+    plhs[0] = mxCreateDoubleMatrix((mwSize)(2 * A), K, mxREAL);
+    for (mwSize i = 0; i < K * (mwSize)(2 * A); ++i) mxGetDoubles(plhs[0])[i] = wf[i];
     return;
   }
   if (!g_ctx) mexErrMsgIdAndTxt("fmcw:state", "call fmcw_mex('init') first");
@@ -625,6 +664,45 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     for (mwSize a = 0; a < A; ++a) chan[a] = mxGetComplexSingles(rd) + a * map;
     for (int b = 0; b < q.n_beam; ++b) out[b] = mxGetComplexSingles(plhs[0]) + (size_t)b * map;
     check(fmcw_beam(g_ctx, &q, chan, FMCW_C64, F, nr, nd, out));
+    return;
+  }
+  if (!strcmp(cmd, "ra")) {                 /* [ra, cov, ra_max] = fmcw_mex('ra', Q, rd4, w) */
+    if (nrhs != 4) mexErrMsgIdAndTxt("fmcw:arg", "ra: Q, rd4, w");
+    const mxArray* s = prhs[1];
+    const mxArray* rd = prhs[2];
+    const mxArray* w = prhs[3];
+    if (!mxIsStruct(s)) mexErrMsgIdAndTxt("fmcw:arg", "Q must be a struct");
+    if (!mxIsSingle(rd) || !mxIsComplex(rd) || mxGetNumberOfDimensions(rd) != 4)
+      mexErrMsgIdAndTxt("fmcw:arg", "rd4 must be single complex Nd x Nr x F x A");
+    const mwSize* dims = mxGetDimensions(rd);
+    const int32_t nd = (int32_t)dims[0], nr = (int32_t)dims[1];
+    const int64_t F = (int64_t)dims[2];
+    const mwSize A = dims[3];
+    if (A < 2 || A > 8 || !mxIsDouble(w) || mxIsComplex(w) || mxGetNumberOfElements(w) == 0 ||
+        mxGetNumberOfElements(w) % (2 * A) || mxGetNumberOfElements(w) > 512 * A)
+      mexErrMsgIdAndTxt("fmcw:arg", "A must be in 2..8 and w a real double array of 2 x A x K values (re, im; plane; direction), K in 1..256");
+    fmcw_ra_params q;
+    memset(&q, 0, sizeof q);
+    q.n_chan = (int32_t)A;
+    q.n_ang = (int32_t)(mxGetNumberOfElements(w) / (2 * A));
+    q.r_lo = (int32_t)field(s, "r_lo");
+    q.r_hi = (int32_t)field(s, "r_hi");
+    q.dc_half = (int32_t)field(s, "dc_half");
+    q.flags = (int32_t)field(s, "flags");
+    q.load = (float)field(s, "load");
+    check(fmcw_ra_check(&q, nr, nd));
+    float* wf = (float*)mxCalloc(mxGetNumberOfElements(w), sizeof(float));   /* freed with the MEX call's memory */
+    for (mwSize i = 0; i < mxGetNumberOfElements(w); ++i) wf[i] = (float)mxGetDoubles(w)[i];
+    const size_t map = (size_t)F * (size_t)nr * (size_t)nd;
+    const mwSize T = A * (A + 1) / 2;
+    plhs[0] = mxCreateNumericMatrix((mwSize)q.n_ang, (mwSize)nr * (mwSize)F, mxSINGLE_CLASS, mxREAL);
+    mxArray* cov = mxCreateNumericMatrix(2 * T, (mwSize)nr * (mwSize)F, mxSINGLE_CLASS, mxREAL);
+    const void* chan[8] = {0};
+    for (mwSize a = 0; a < A; ++a) chan[a] = mxGetComplexSingles(rd) + a * map;
+    float mx = 0.f;
+    check(fmcw_ra(g_ctx, &q, chan, FMCW_C64, F, nr, nd, wf, mxGetSingles(cov), mxGetSingles(plhs[0]), &mx));
+    if (nlhs > 1) plhs[1] = cov;
+    if (nlhs > 2) plhs[2] = mxCreateDoubleScalar((double)mx);
     return;
   }
   mexErrMsgIdAndTxt("fmcw:arg", "unknown command '%s'", cmd);
