@@ -21,11 +21,13 @@ ABI_VERSION = 4
 STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_HIP", -3: "E_OOM", -4: "E_STATE", -5: "E_DATA"}
 STAGES = ("range", "doppler", "detect", "compact", "stft_power", "stft_db", "range_only", "range_doppler", "onepass",
           "render", "cfar", "cluster", "track", "mti", "aoa", "beam", "oscfar", "ra")
+MUSIC_STAGE = 18           # fmcw_timing_read's stage of fmcw_music_device ("music" in Engine.timing_read)
 FMCW_CFAR_LOCAL_MAX = 1
 FMCW_SIG_DB = 1
 FMCW_MTI_RAMP, FMCW_MTI_FREEZE = 1, 2
 FMCW_BEAM_NCI = 1
 FMCW_RA_CAPON = 1
+FMCW_MUSIC_FB = 1
 
 
 class FmcwError(RuntimeError):
@@ -132,6 +134,13 @@ class RaParams(ct.Structure):
                 ("dc_half", ct.c_int32), ("flags", ct.c_int32), ("load", ct.c_float)]
 
 
+class MusicParams(ct.Structure):
+    """fmcw_music_params (include/fmcw.h)."""
+    _fields_ = [("n_chan", ct.c_int32), ("n_ang", ct.c_int32), ("r_lo", ct.c_int32), ("r_hi", ct.c_int32),
+                ("n_src", ct.c_int32), ("max_src", ct.c_int32), ("sweeps", ct.c_int32), ("flags", ct.c_int32),
+                ("src_thr", ct.c_float)]
+
+
 class JsonField(ct.Structure):
     """fmcw_json_field (include/fmcw.h)."""
     _fields_ = [("name", ct.c_char_p), ("kind", ct.c_int32), ("data", ct.c_void_p),
@@ -222,6 +231,9 @@ SIGNATURES = {
     "fmcw_cov_device": (ct.c_int, [_P, ct.POINTER(RaParams), ct.POINTER(_P), _I32, _I64, _I32, _I32, _P, _P]),
     "fmcw_ra_device": (ct.c_int, [_P, ct.POINTER(RaParams), _P, _I64, _I32, _P, _P, _P, _P]),
     "fmcw_ra": (ct.c_int, [_P, ct.POINTER(RaParams), ct.POINTER(_P), _I32, _I64, _I32, _I32, _P, _P, _P, _P]),
+    "fmcw_music_check": (ct.c_int, [ct.POINTER(MusicParams), _I32]),
+    "fmcw_music_device": (ct.c_int, [_P, ct.POINTER(MusicParams), _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "fmcw_music": (ct.c_int, [_P, ct.POINTER(MusicParams), _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
     "fmcw_json_write": (ct.c_int, [ct.c_char_p, ct.POINTER(JsonField), _I32, _I32, _I32, ct.POINTER(_I64)]),
     "fmcw_stft_png": (ct.c_int, [_P, _P, _I64, _P, _I32, _I32, _I32, _D, _I32, _P, _P, _P, ct.c_char_p, _I32, _I32,
                                  ct.POINTER(_I64)]),

@@ -127,7 +127,7 @@ inline void shard(int64_t total, int g, int world, int64_t& f0, int64_t& n) {
   n = base + (g < rem ? 1 : 0);
 }
 
-constexpr int kStages = 18;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar, 11 cluster, 12 track, 13 mti, 14 aoa, 15 beam, 16 oscfar, 17 ra
+constexpr int kStages = 19;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar, 11 cluster, 12 track, 13 mti, 14 aoa, 15 beam, 16 oscfar, 17 ra, 18 music
 
 }  // namespace fmcw
 
@@ -267,6 +267,9 @@ struct fmcw_ctx {
   // fmcw_ra (host pointers): the chunk's frames of every channel, its covariances and its spectra, and the
   // weight table with the running maximum on the device
   DevBuf ra_rd, ra_cov, ra_out, ra_w;
+  // fmcw_music (host pointers): the chunk's covariances, its four outputs, and the weight table with the
+  // running maximum on the device
+  DevBuf mu_cov, mu_eval, mu_evec, mu_nsrc, mu_out, mu_w;
   int64_t chunk_frames = 0;
   int64_t last_coarse_tiles = -1;     // tiles the last coarse-to-fine max(P) evaluated in full (diagnostics)
   int pipe_mode = FMCW_PIPE_AUTO;

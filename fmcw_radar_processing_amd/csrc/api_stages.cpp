@@ -1443,4 +1443,137 @@ int fmcw_ra(fmcw_ctx* c, const fmcw_ra_params* q, const void* const* rd_ch, int3
   return FMCW_OK;
 }
 
+// ---------------------------------------------------------------------------
+// MUSIC: per range row the eigen-decomposition of its covariance, a source count and the MUSIC
+// pseudo-spectrum (kernels_music.hip)
+// ---------------------------------------------------------------------------
+int fmcw_music_check(const fmcw_music_params* q, int32_t nr) {
+  if (!q) return fail(FMCW_E_ARG, "music params is NULL");
+  CHK(check_rd_shape("music", nr, 4));
+  CHK(check_gate("music", q->r_lo, q->r_hi, nr));
+  if (q->n_chan < 2 || q->n_chan > fmcw::kRaChan) return fail(FMCW_E_ARG, "music: n_chan must be in [2, 8]");
+  if (q->n_ang < 1 || q->n_ang > fmcw::kRaAngMax) return fail(FMCW_E_ARG, "music: n_ang must be in [1, 256]");
+  if (q->n_src < 0 || q->n_src >= q->n_chan) return fail(FMCW_E_ARG, "music: n_src must be in [0, n_chan - 1] (0 estimates it)");
+  if (q->n_src == 0 && (q->max_src < 1 || q->max_src >= q->n_chan))
+    return fail(FMCW_E_ARG, "music: max_src must be in [1, n_chan - 1] when n_src is 0");
+  if (q->sweeps < 1 || q->sweeps > 16) return fail(FMCW_E_ARG, "music: sweeps must be in [1, 16]");
+  if (q->flags & ~FMCW_MUSIC_FB) return fail(FMCW_E_ARG, "music: unknown flag bits");
+  if (!(std::isfinite(q->src_thr) && q->src_thr > 0.f)) return fail(FMCW_E_ARG, "music: src_thr must be finite and > 0");
+  return FMCW_OK;
+}
+
+static int music_entry(fmcw_ctx* c, const fmcw_music_params* q, int64_t F, int32_t nr) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(fmcw_music_check(q, nr));
+  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
+  if (F > ((int64_t)1 << 40)) return fail(FMCW_E_ARG, "music: F must be at most 2^40");
+  return FMCW_OK;
+}
+
+int fmcw_music_device(fmcw_ctx* c, const fmcw_music_params* q, const float* d_cov, int64_t F, int32_t nr, const float* d_w,
+                      float* d_eval, float* d_evec, int32_t* d_nsrc, float* d_music, float* d_music_max, void* stream) {
+  CHK(music_entry(c, q, F, nr));
+  if (!d_eval && !d_evec && !d_nsrc && !d_music) return fail(FMCW_E_ARG, "music: every output is NULL");
+  if (F == 0) return FMCW_OK;
+  if (!d_cov || (d_music && !d_w)) return fail(FMCW_E_ARG, "required pointer is NULL");
+  if ((reinterpret_cast<uintptr_t>(d_cov) | reinterpret_cast<uintptr_t>(d_w) | reinterpret_cast<uintptr_t>(d_eval) |
+       reinterpret_cast<uintptr_t>(d_evec) | reinterpret_cast<uintptr_t>(d_nsrc) | reinterpret_cast<uintptr_t>(d_music)) & 15)
+    return fail(FMCW_E_ARG, "music: d_cov, d_w, d_eval, d_evec, d_nsrc and d_music must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_music_max) & 3) return fail(FMCW_E_ARG, "music: d_music_max must be 4-byte aligned");
+  CHK(set_device(c));
+  hipStream_t s = pick(c, stream);
+  fmcw::MusicArgs a{};
+  a.A = q->n_chan; a.NR = nr; a.n_ang = q->n_ang;
+  gate_rows(q->r_lo, q->r_hi, nr, a.g0, a.g1);
+  a.n_src = q->n_src;
+  a.max_src = q->n_src ? 1 : q->max_src;
+  a.sweeps = q->sweeps;
+  a.fb = (q->flags & FMCW_MUSIC_FB) ? 1 : 0;
+  a.src_thr = q->src_thr;
+  a.w = d_music ? d_w : nullptr;
+  a.music_max = d_music ? d_music_max : nullptr;
+  const size_t A = (size_t)a.A, T = A * (A + 1) / 2;
+  // at most kRaRowsMax rows per launch (the results do not depend on the cut)
+  const int64_t Fc = fmcw::kRaRowsMax / nr;
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    a.rows = std::min(Fc, F - f0) * nr;
+    const size_t r0 = (size_t)f0 * nr;
+    a.cov = d_cov + r0 * T * 2;
+    a.eval = shifted(d_eval, (int64_t)(r0 * A));
+    a.evec = shifted(d_evec, (int64_t)(r0 * A * A * 2));
+    a.nsrc = shifted(d_nsrc, (int64_t)r0);
+    a.music = shifted(d_music, (int64_t)(r0 * a.n_ang));
+    StageTimer tm(c, 18, s);
+    HIPCHK(fmcw::launch_music(a, s));
+    tm.done();
+  }
+  return FMCW_OK;
+}
+
+// One shard of fmcw_music, chunk by chunk: the chunk's covariances in, what was asked for out.
+static int music_host_one(fmcw_ctx* c, const fmcw_music_params* q, const float* cov, int64_t F, int32_t nr, const float* w,
+                          float* eval, float* evec, int32_t* nsrc, float* music, float* mx) {
+  CHK(set_device(c));
+  hipStream_t s = c->stream;
+  const size_t A = (size_t)q->n_chan, K = (size_t)q->n_ang;
+  const size_t covf = (size_t)nr * A * (A + 1), evf = (size_t)nr * A, vecf = (size_t)nr * A * A * 2, muf = (size_t)nr * K;   // per frame
+  const int64_t Fc = host_chunk(covf * 4, F);
+  Arena ar;
+  const size_t o_w = ar.add(K * A * 8), o_mx = ar.add(4);
+  CHK(c->mu_cov.ensure((size_t)Fc * covf * 4));
+  if (eval) CHK(c->mu_eval.ensure((size_t)Fc * evf * 4));
+  if (evec) CHK(c->mu_evec.ensure((size_t)Fc * vecf * 4));
+  if (nsrc) CHK(c->mu_nsrc.ensure((size_t)Fc * nr * 4));
+  float* d_w = nullptr;
+  float* d_mx = nullptr;
+  if (music) {
+    CHK(c->mu_out.ensure((size_t)Fc * muf * 4));
+    CHK(c->mu_w.ensure(ar.off));
+    d_w = reinterpret_cast<float*>(c->mu_w.as<char>() + o_w);
+    d_mx = reinterpret_cast<float*>(c->mu_w.as<char>() + o_mx);
+    HIPCHK(hipMemsetAsync(d_mx, 0, 4, s));
+    HIPCHK(hipMemcpyAsync(d_w, w, K * A * 8, hipMemcpyHostToDevice, s));
+  }
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    const int64_t nf = std::min(Fc, F - f0);
+    HIPCHK(hipMemcpyAsync(c->mu_cov.p, cov + (size_t)f0 * covf, (size_t)nf * covf * 4, hipMemcpyHostToDevice, s));
+    CHK(fmcw_music_device(c, q, c->mu_cov.as<float>(), nf, nr, d_w, eval ? c->mu_eval.as<float>() : nullptr,
+                          evec ? c->mu_evec.as<float>() : nullptr, nsrc ? c->mu_nsrc.as<int32_t>() : nullptr,
+                          music ? c->mu_out.as<float>() : nullptr, d_mx, s));
+    if (eval) HIPCHK(hipMemcpyAsync(eval + (size_t)f0 * evf, c->mu_eval.p, (size_t)nf * evf * 4, hipMemcpyDeviceToHost, s));
+    if (evec) HIPCHK(hipMemcpyAsync(evec + (size_t)f0 * vecf, c->mu_evec.p, (size_t)nf * vecf * 4, hipMemcpyDeviceToHost, s));
+    if (nsrc) HIPCHK(hipMemcpyAsync(nsrc + (size_t)f0 * nr, c->mu_nsrc.p, (size_t)nf * nr * 4, hipMemcpyDeviceToHost, s));
+    if (music) HIPCHK(hipMemcpyAsync(music + (size_t)f0 * muf, c->mu_out.p, (size_t)nf * muf * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));           // the chunk buffers are reused by the next chunk
+  }
+  *mx = 0.f;
+  if (music) HIPCHK(hipMemcpyAsync(mx, d_mx, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return FMCW_OK;
+}
+
+int fmcw_music(fmcw_ctx* c, const fmcw_music_params* q, const float* cov, int64_t F, int32_t nr, const float* w, float* eval,
+               float* evec, int32_t* nsrc, float* music, float* music_max) {
+  CHK(music_entry(c, q, F, nr));
+  if (!eval && !evec && !nsrc && !music) return fail(FMCW_E_ARG, "music: every output is NULL");
+  if (F == 0) {
+    if (music_max) *music_max = 0.f;
+    return FMCW_OK;
+  }
+  if (!cov || (music && !w)) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const int64_t A = q->n_chan;
+  const int64_t covf = (int64_t)nr * A * (A + 1), evf = (int64_t)nr * A, vecf = (int64_t)nr * A * A * 2, muf = (int64_t)nr * q->n_ang;
+  const int world = 1 + (int)c->peers.size();
+  std::vector<float> mx((size_t)world, 0.f);
+  // frames are independent: contiguous shards, each written in place
+  CHK(over_devices(c, F, [&](fmcw_ctx* d, int g, int64_t f0, int64_t n) {
+    return music_host_one(d, q, cov + f0 * covf, n, nr, w, shifted(eval, f0 * evf), shifted(evec, f0 * vecf),
+                          shifted(nsrc, f0 * nr), shifted(music, f0 * muf), &mx[(size_t)g]);
+  }));
+  float gmx = 0.f;                             // a maximum of non-negative floats does not depend on order
+  for (int g = 0; g < world; ++g) gmx = std::max(gmx, mx[(size_t)g]);
+  if (music_max) *music_max = gmx;
+  return FMCW_OK;
+}
+
 }  // extern "C"

@@ -479,6 +479,26 @@ struct RaArgs {
 };
 hipError_t launch_ra(const RaArgs& a, hipStream_t s);
 
+// MUSIC (kernels_music.hip): k_music (per range row the eigen-decomposition of its covariance, a
+// source count and the MUSIC pseudo-spectrum)
+struct MusicArgs {
+  const float* cov;                // [rows][T][2]; 8-byte aligned
+  const float* w;                  // [n_ang][A][2]; read only with music
+  float* eval;                     // [rows][A] or nullptr
+  float* evec;                     // [rows][A][A][2] or nullptr
+  int32_t* nsrc;                   // [rows] or nullptr
+  float* music;                    // [rows][n_ang] or nullptr
+  float* music_max;                // running maximum or nullptr
+  int64_t rows;
+  int A, NR, n_ang;
+  int g0, g1;
+  int n_src, max_src;              // n_src 0: estimated, at most max_src
+  int sweeps;
+  int fb;                          // forward-backward averaging
+  float src_thr;
+};
+hipError_t launch_music(const MusicArgs& a, hipStream_t s);
+
 bool range_size_supported(int nr);
 bool doppler_size_supported(int nd);
 

@@ -16,8 +16,8 @@ import ctypes as ct
 import numpy as np
 
 from . import _lib
-from ._lib import FMCW_C32H, FMCW_C64, STAGES, FmcwError, check
-from .params import (AoaConfig, BeamConfig, CfarConfig, ClusterConfig, FmcwConfig, MtiConfig, OsCfarConfig, RaConfig,
+from ._lib import FMCW_C32H, FMCW_C64, MUSIC_STAGE, STAGES, FmcwError, check
+from .params import (AoaConfig, BeamConfig, CfarConfig, ClusterConfig, FmcwConfig, MtiConfig, MusicConfig, OsCfarConfig, RaConfig,
                      SigConfig, TrackConfig)
 
 
@@ -809,6 +809,77 @@ class Engine:
             check(self.lib.fmcw_ra_device(self.h, ct.byref(qa), _ptr(d_cov), int(F), int(nr), _ptr(d_w), _ptr(d_ra),
                                           _ptr(d_ra_max), hs))
 
+    # ---- MUSIC: eigen-decomposition of the rows' covariance, source count, pseudo-spectrum (fmcw_music_params) ----
+    def music_device(self, q: MusicConfig, d_cov, F: int, nr: int, d_w=None, d_eval=None, d_evec=None, d_nsrc=None,
+                     d_music=None, d_music_max=None, stream=None) -> None:
+        """fmcw_music_device: d_cov float32 [F][nr][T][2] (of cov_device, or the caller's own); d_w
+        float32 [q.n_ang][q.n_chan][2], needed with d_music; d_eval float32 [F][nr][A], d_evec float32
+        [F][nr][A][A][2], d_nsrc int32 [F][nr], d_music float32 [F][nr][q.n_ang], any of them None but
+        not all; d_music_max one float32 zeroed by the caller, or None.  q: a MusicConfig, or the C
+        struct _lib.MusicParams itself.  Asynchronous on `stream`."""
+        qa = q.abi() if hasattr(q, "abi") else q
+        with _sided(stream) as hs:
+            check(self.lib.fmcw_music_device(self.h, ct.byref(qa), _ptr(d_cov), int(F), int(nr), _ptr(d_w), _ptr(d_eval),
+                                             _ptr(d_evec), _ptr(d_nsrc), _ptr(d_music), _ptr(d_music_max), hs))
+
+    def music_host(self, cov, q: MusicConfig, w=None, want=("eval", "evec", "nsrc", "music")) -> dict:
+        """fmcw_music on a host covariance float32 [F][nr][T][2]: dict(eval, evec, nsrc, music,
+        music_max) with None for what `want` leaves out.  Frames sharded over the context's devices."""
+        cov = np.ascontiguousarray(cov, np.float32)
+        A, K = int(q.n_chan), int(q.n_ang)
+        if cov.ndim != 4 or cov.shape[2:] != (A * (A + 1) // 2, 2):
+            raise ValueError("music: cov must be [F][nr][n_chan (n_chan + 1) / 2][2]")
+        F, nr = cov.shape[:2]
+        wf = None
+        if "music" in want:
+            if w is None:
+                raise ValueError("music: the spectrum needs a weight table (Engine.ra_weights)")
+            wf = np.ascontiguousarray(np.asarray(w).astype(np.complex64))
+            if wf.shape != (K, A):
+                raise ValueError("music: w must be [q.n_ang][q.n_chan] complex")
+        out = {"eval": np.empty((F, nr, A), np.float32) if "eval" in want else None,
+               "evec": np.empty((F, nr, A, A, 2), np.float32) if "evec" in want else None,
+               "nsrc": np.empty((F, nr), np.int32) if "nsrc" in want else None,
+               "music": np.empty((F, nr, K), np.float32) if "music" in want else None}
+        mx = ct.c_float(0.0)
+        qa = q.abi()
+        check(self.lib.fmcw_music(self.h, ct.byref(qa), _ptr(cov), F, nr, _ptr(wf), _ptr(out["eval"]), _ptr(out["evec"]),
+                                  _ptr(out["nsrc"]), _ptr(out["music"]), ct.byref(mx)))
+        out["music_max"] = float(mx.value)
+        return out
+
+    def music(self, rds, q: MusicConfig, ra_q: RaConfig, w) -> dict:
+        """The q.n_chan RD maps `rds` (host arrays, as range_angle takes them) -> cov_device with ra_q
+        (its dc_half and gate), then music_device with q, on the context's first device: dict(cov, eval,
+        evec, nsrc, music, music_max) of numpy arrays.  w: complex [q.n_ang][q.n_chan] of ra_weights."""
+        import torch
+        chans = [_host_rd(rd, "F") for rd in rds]
+        A, K = int(q.n_chan), int(q.n_ang)
+        if len(chans) != A or int(ra_q.n_chan) != A:
+            raise ValueError("music: rds must hold q.n_chan maps and ra_q.n_chan must equal q.n_chan")
+        dt = chans[0][1]
+        if any(c[1] != dt or c[0].shape != chans[0][0].shape for c in chans):
+            raise ValueError("music: the channels must share one dtype and shape")
+        F, nr, nd = chans[0][0].shape[:3]
+        wf = np.ascontiguousarray(np.asarray(w).astype(np.complex64))
+        if wf.shape != (K, A):
+            raise ValueError("music: w must be [q.n_ang][q.n_chan] complex")
+        dev = torch.device("cuda", self.device)
+        d_rds = [torch.from_numpy(np.array(c[0])).to(dev) for c in chans]      # a copy: the caller's array may be read-only
+        d_w = torch.from_numpy(wf.view(np.float32).reshape(K, A, 2)).to(dev)
+        d_cov = torch.empty((F, nr, A * (A + 1) // 2, 2), dtype=torch.float32, device=dev)
+        d_eval = torch.empty((F, nr, A), dtype=torch.float32, device=dev)
+        d_evec = torch.empty((F, nr, A, A, 2), dtype=torch.float32, device=dev)
+        d_nsrc = torch.empty((F, nr), dtype=torch.int32, device=dev)
+        d_music = torch.empty((F, nr, K), dtype=torch.float32, device=dev)
+        d_mx = torch.zeros(1, dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.cov_device(ra_q, d_rds, dt, F, nr, nd, d_cov)
+        self.music_device(q, d_cov, F, nr, d_w, d_eval, d_evec, d_nsrc, d_music, d_mx)
+        self.synchronize()
+        return {"cov": d_cov.cpu().numpy(), "eval": d_eval.cpu().numpy(), "evec": d_evec.cpu().numpy(),
+                "nsrc": d_nsrc.cpu().numpy(), "music": d_music.cpu().numpy(), "music_max": float(d_mx.cpu()[0])}
+
     # ---- timing -----------------------------------------------------------------
     def timing(self, level: int) -> None:
         """0 off, 1 per range+Doppler chunk + STFT launches, 2 per kernel launch, 3 the dominant
@@ -820,7 +891,7 @@ class Engine:
 
     def timing_read(self) -> dict:
         out = {}
-        for i, name in enumerate(STAGES):
+        for i, name in list(enumerate(STAGES)) + [(MUSIC_STAGE, "music")]:
             ms, n = ct.c_double(), ct.c_int64()
             check(self.lib.fmcw_timing_read(self.h, i, ct.byref(ms), ct.byref(n)))
             out[name] = (ms.value, n.value)

@@ -12,8 +12,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import windows
-from ._lib import (FMCW_BEAM_NCI, FMCW_CFAR_LOCAL_MAX, FMCW_MTI_FREEZE, FMCW_MTI_RAMP, FMCW_RA_CAPON, FMCW_SIG_DB, AoaParams,
-                   BeamParams, CfarParams, ClusterParams, MtiParams, OsCfarParams, Params, RaParams, SigParams, TrackParams)
+from ._lib import (FMCW_BEAM_NCI, FMCW_CFAR_LOCAL_MAX, FMCW_MTI_FREEZE, FMCW_MTI_RAMP, FMCW_MUSIC_FB, FMCW_RA_CAPON, FMCW_SIG_DB,
+                   AoaParams, BeamParams, CfarParams, ClusterParams, MtiParams, MusicParams, OsCfarParams, Params, RaParams, SigParams, TrackParams)
 
 C0 = 3e8  # radar_processing.m:67
 
@@ -645,3 +645,51 @@ class RaConfig:
             load = np.float32(self.load)
         if not (np.isfinite(load) and load >= 0):
             raise ValueError("ra: load must be finite and >= 0")
+
+
+@dataclass
+class MusicConfig:
+    """fmcw_music_params (include/fmcw.h): MUSIC angular spectra from the covariance of every range
+    row (what RaConfig's covariance stage writes).  Per row the eigen-decomposition by `sweeps` cyclic
+    Jacobi sweeps, a source count (n_src, or with n_src = 0 the number of eigenvalues above src_thr
+    times the mean of the n_chan - max_src smallest, at most max_src) and the pseudo-spectrum over
+    n_ang look directions (a weight table of Engine.ra_weights).  fb: forward-backward averaging,
+    for a uniform line; it separates returns of one Doppler bin.  The gate r_lo..r_hi is 1-based and
+    inclusive, (0, 0) = every row; rows outside it are zero."""
+    n_chan: int
+    n_ang: int
+    r_lo: int = 0
+    r_hi: int = 0
+    n_src: int = 0
+    max_src: int = 1
+    sweeps: int = 8
+    fb: bool = False
+    src_thr: float = 8.0
+
+    def abi(self) -> MusicParams:
+        return MusicParams(int(self.n_chan), int(self.n_ang), int(self.r_lo), int(self.r_hi), int(self.n_src),
+                           int(self.max_src), int(self.sweeps), FMCW_MUSIC_FB if self.fb else 0, self.src_thr)
+
+    def validate(self, nr: int) -> None:
+        """The rules of fmcw_music_check, on the float32 value the C struct carries; ValueError
+        naming the first one violated."""
+        if nr < 16 or nr > 2048 or nr & (nr - 1):
+            raise ValueError("music: nr must be a power of two in [16, 2048]")
+        if self.r_lo > self.r_hi:
+            raise ValueError("music: r_lo > r_hi")
+        if (self.r_lo, self.r_hi) != (0, 0) and (self.r_lo < 1 or self.r_hi > nr):
+            raise ValueError("music: the gate r_lo..r_hi must lie in 1..nr (or be 0, 0 for all rows)")
+        if not 2 <= self.n_chan <= 8:
+            raise ValueError("music: n_chan must be in [2, 8]")
+        if not 1 <= self.n_ang <= 256:
+            raise ValueError("music: n_ang must be in [1, 256]")
+        if not 0 <= self.n_src <= self.n_chan - 1:
+            raise ValueError("music: n_src must be in [0, n_chan - 1] (0 estimates it)")
+        if self.n_src == 0 and not 1 <= self.max_src <= self.n_chan - 1:
+            raise ValueError("music: max_src must be in [1, n_chan - 1] when n_src is 0")
+        if not 1 <= self.sweeps <= 16:
+            raise ValueError("music: sweeps must be in [1, 16]")
+        with np.errstate(over="ignore"):
+            thr = np.float32(self.src_thr)
+        if not (np.isfinite(thr) and thr > 0):
+            raise ValueError("music: src_thr must be finite and > 0")

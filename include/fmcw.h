@@ -60,7 +60,9 @@ extern "C" {
  *    fmcw_oscfar_device, fmcw_oscfar), the struct fmcw_oscfar_params and timing stage 16, added
  *    within ABI 4 in the same way
  *    + the range-angle entry points (fmcw_ra_check, fmcw_ra_steer, fmcw_cov_device, fmcw_ra_device,
- *    fmcw_ra), the struct fmcw_ra_params and timing stage 17, added within ABI 4 in the same way */
+ *    fmcw_ra), the struct fmcw_ra_params and timing stage 17, added within ABI 4 in the same way
+ *    + the MUSIC entry points (fmcw_music_check, fmcw_music_device, fmcw_music), the struct
+ *    fmcw_music_params and timing stage 18, added within ABI 4 in the same way */
 #define FMCW_ABI_VERSION 4
 
 typedef enum fmcw_status {
@@ -295,7 +297,8 @@ int fmcw_synth_device(fmcw_ctx* ctx, const fmcw_params* p, int64_t frame0, int64
  *        per k_aoa launch of fmcw_aoa_device), 15 beam (one pair per k_beam launch of
  *        fmcw_beam_device), 16 oscfar (one pair per k_oscfar + k_cfar_gather + k_oscfar_select
  *        launch group of fmcw_oscfar_device), 17 ra (one pair per k_cov launch of fmcw_cov_device
- *        and one per k_ra launch of fmcw_ra_device).
+ *        and one per k_ra launch of fmcw_ra_device), 18 music (one pair per k_music launch of
+ *        fmcw_music_device).
  *        fmcw_timing_read synchronises. */
 int fmcw_timing_enable(fmcw_ctx* ctx, int32_t enable);
 int fmcw_timing_read(fmcw_ctx* ctx, int32_t stage, double* total_ms, int64_t* launches);
@@ -988,7 +991,7 @@ int fmcw_beam(fmcw_ctx* ctx, const fmcw_beam_params* q, const void* const* rd_ch
  * and Capon (MVDR) angular power spectra taken from it (added within ABI 4; beyond the reference).
  * fmcw_aoa* gives one angle per detection and fmcw_beam* at most eight fixed beams; this stage gives
  * an angular spectrum for every range row on a grid of up to 256 look directions, and the covariance
- * itself, which is the input of any subspace method.  Indices below are 0-based; the gate is 1-based
+ * itself, which is the input of any subspace method (fmcw_music* below is one).  Indices below are 0-based; the gate is 1-based
  * as everywhere else.
  *   Input: A channel maps rd[a], A in 2..8, each [F][nr][nd], all FMCW_C64 or all FMCW_C32H, given as
  *     a host array of A pointers exactly as fmcw_beam takes them (device call: each 16-byte aligned);
@@ -1085,6 +1088,97 @@ int fmcw_ra_device(fmcw_ctx* ctx, const fmcw_ra_params* q, const float* d_cov, i
  * ra; *ra_max (may be NULL) is the maximum over all shards, 0 without ra. */
 int fmcw_ra(fmcw_ctx* ctx, const fmcw_ra_params* q, const void* const* rd_ch, int32_t rd_dtype, int64_t F,
             int32_t nr, int32_t nd, const float* w, float* cov, float* ra, float* ra_max);
+
+/* ---------------------------------------------------------------------------
+ * MUSIC angular spectra: per range row the eigen-decomposition of its spatial covariance, a source
+ * count and the MUSIC pseudo-spectrum (added within ABI 4; beyond the reference).  Bartlett cannot
+ * separate two returns closer than the array's beamwidth and Capon only sometimes; the noise
+ * subspace of the covariance can, and with forward-backward averaging it also separates two
+ * returns of one Doppler bin (coherent ones) on a uniform line.
+ *   Input: cov [F][nr][T][2] float32, T = A (A + 1) / 2, A in 2..8: exactly what fmcw_cov_device
+ *     writes, or a caller's own covariance in that layout; nr within CFAR's limits.
+ *   Outputs, all float32 but nsrc; rows outside the gate r_lo..r_hi are zero in every one of them:
+ *     eval [F][nr][A]          the eigenvalues, ascending;
+ *     evec [F][nr][A][A][2]    evec[j][a] = component a of the eigenvector of eval[j], (re, im);
+ *     nsrc [F][nr] int32       the source count n;
+ *     music [F][nr][n_ang]     the pseudo-spectrum on the look directions of a weight table
+ *                              w [n_ang][A][2] of fmcw_ra_steer, n_ang in 1..256.
+ *   Everything is float32, every operation rounded on its own in the order written (no fused
+ *   multiply-add), divides and square roots correctly rounded: every output byte equals a float32
+ *   numpy evaluation of the steps below on the same cov bytes, for any F and any sharding or
+ *   chunking, and does not depend on which other outputs were asked for.
+ *   1. Matrix.  The state is the upper triangle: M_ab, a <= b, is the packed entry; a diagonal
+ *      entry's imaginary part is not read (it is taken as +0).  Wherever M_ba, b > a, is read it is
+ *      conj(M_ab), and where it is written M_ab becomes its conjugate: there is one copy of every pair.
+ *      With FMCW_MUSIC_FB (forward-backward averaging, for a uniform line) every upper entry is first
+ *      replaced from the ORIGINAL R by 0.5f (R_ab + R_a'b'), a' = A-1-b, b' = A-1-a (also an upper
+ *      entry: no conjugate), re and im each on its own; a diagonal entry's im stays +0.
+ *   2. Cyclic Jacobi, `sweeps` sweeps, no data-dependent stopping (the call ends for any bytes).
+ *      V = I.  sweeps times: for p = 0..A-2, for q = p+1..A-1:
+ *        h = M_pq;  g = sqrtf(h.re h.re + h.im h.im);  the pair is SKIPPED iff g == 0;
+ *        ph = (h.re / g, h.im / g);  a = M_pp.re, b = M_qq.re;
+ *        tau = (b - a) / (2 g);  at = |tau|;  t = 1 / (at + sqrtf(1 + at at)), negated when tau < 0;
+ *        c = 1 / sqrtf(1 + t t);  s = t c;  sp = (s ph.re, s ph.im).
+ *        For every k other than p and q, with x = M_kp, y = M_kq:
+ *          M_kp = (c x.re - (sp.re y.re + sp.im y.im),  c x.im - (sp.re y.im - sp.im y.re))
+ *          M_kq = ((sp.re x.re - sp.im x.im) + c y.re,  (sp.re x.im + sp.im x.re) + c y.im)
+ *        (c x - conj(sp) y and sp x + c y, four real products per complex product, each pair's sum
+ *        or difference rounded, then combined with the c term), and M_pk = conj(M_kp),
+ *        M_qk = conj(M_kq).  Then M_pp = a - t g, M_qq = b + t g (one product t g), M_pq = (+0, +0).
+ *        The same two expressions update V_kp, V_kq for EVERY k = 0..A-1.
+ *        tau = +-inf gives t = 0: overflow needs no special case.
+ *   3. Order.  lambda_j: the diagonal entries ascending, ties by original index; e_j the matching
+ *      column of V.
+ *   4. Source count.  n_src in 1..A-1: n = n_src.  n_src = 0: nu = (lambda_0 + ... +
+ *      lambda_{A-max_src-1}, added ascending from 0) / (float)(A - max_src);
+ *      n = min(max_src, #{j : lambda_j > src_thr nu}), in 0..max_src.
+ *   5. MUSIC, per direction k, w = w[k]:  e = sum_a (w_a.re w_a.re + w_a.im w_a.im), ascending from 0;
+ *      den = 0; for j = 0..A-n-1: p = (0, 0); for a ascending, v = e_j[a]:
+ *        p.re += (w_a.re v.re - w_a.im v.im);  p.im += (w_a.re v.im + w_a.im v.re);
+ *      den += (p.re p.re + p.im p.im).  music = e / den, FLT_MAX when den == 0.
+ *      With w = conj(a) / A this is the usual a^H a / (a^H E_n E_n^H a).
+ *   6. d_music_max: an optional running maximum of everything written to music, kept exactly as
+ *      fmcw_ra_device's d_ra_max (an integer atomic maximum on the float's bits; the caller zeroes it).
+ *   A zero row skips every rotation: lambda = 0, V = I; an estimated n is then 0 and music is 1.
+ *   A non-finite input makes that row's outputs unspecified; it touches nothing else and nothing out
+ *   of bounds.
+ *   Accuracy against a float64 eigh, the rows where it is lost (equal diagonal entries under an
+ *   off-diagonal entry whose square is denormal), the default of sweeps and the measured times:
+ *   DESIGN.md 4.13, profiles/music_bench.json.
+ *   Parameters: n_chan = A in 2..8; n_ang in 1..256; r_lo, r_hi as fmcw_cfar_params; n_src in
+ *     0..A-1 (0: estimated); max_src in 1..A-1, read only when n_src = 0; sweeps in 1..16; flags 0 or
+ *     FMCW_MUSIC_FB (an unknown bit is FMCW_E_ARG); src_thr finite and > 0.
+ * ------------------------------------------------------------------------- */
+enum { FMCW_MUSIC_FB = 1 };
+typedef struct fmcw_music_params {
+  int32_t n_chan;          /* A, 2..8 */
+  int32_t n_ang;           /* look directions, 1..256 */
+  int32_t r_lo, r_hi;      /* range gate, 1-based inclusive; 0, 0: all rows */
+  int32_t n_src;           /* sources, 1..A-1; 0: estimated per row */
+  int32_t max_src;         /* the estimate's upper limit, 1..A-1 (read only when n_src = 0) */
+  int32_t sweeps;          /* Jacobi sweeps, 1..16 */
+  int32_t flags;           /* 0 or FMCW_MUSIC_FB */
+  float   src_thr;         /* the estimate's threshold over the mean of the smallest eigenvalues; > 0 */
+} fmcw_music_params;
+
+/* Host only, no context: FMCW_E_ARG (with a message) for any violation of the constraints. */
+int fmcw_music_check(const fmcw_music_params* q, int32_t nr);
+
+/* Device pointers (every one given 16-byte aligned; *q is read on the host), asynchronous on
+ * `stream`; needs no fmcw_set_taps.  Acts on the context's first device.  d_cov [F][nr][T][2];
+ * d_w [n_ang][n_chan][2], needed only with d_music; d_eval, d_evec, d_nsrc, d_music as above, any of
+ * them NULL (not written) but not all; d_music_max one float or NULL, raised only with d_music.
+ * F = 0 is a no-op.  FMCW_E_ARG is returned before any launch: the outputs are then untouched. */
+int fmcw_music_device(fmcw_ctx* ctx, const fmcw_music_params* q, const float* d_cov, int64_t F, int32_t nr,
+                      const float* d_w, float* d_eval, float* d_evec, int32_t* d_nsrc, float* d_music,
+                      float* d_music_max, void* stream);
+
+/* Host pointers (no alignment asked for): staged, frames sharded over the context's devices and
+ * chunked as fmcw_ra is (bit-identical shards and chunks); returns when the outputs are on the host.
+ * Any output may be NULL, not all; w may be NULL without music; *music_max (may be NULL) is the
+ * maximum over all shards, 0 without music. */
+int fmcw_music(fmcw_ctx* ctx, const fmcw_music_params* q, const float* cov, int64_t F, int32_t nr, const float* w,
+               float* eval, float* evec, int32_t* nsrc, float* music, float* music_max);
 
 /* ---------------------------------------------------------------------------
  * spectrogram.png, replacing radar_processing.m:331-348:

@@ -102,6 +102,17 @@
  *   w = fmcw_mex('ra_steer', n_chan, spacing, sin_theta[, cal, taper, normalize])
  *                                                                 -> fmcw_ra_steer (needs no context): 'beam_steer' for up
  *                                        to 256 look directions; w is (2*A) x K, double
+ *   [music, nsrc, eval, evec, music_max] = fmcw_mex('music', Q, cov, nr, w)
+ *                                                                 -> fmcw_music: MUSIC angular spectra (beyond the
+ *                                        reference) from the covariance 'ra' returns: per range row the
+ *                                        eigen-decomposition, a source count and the pseudo-spectrum over the look
+ *                                        directions of w; Q: a struct with the fields r_lo, r_hi, n_src, max_src,
+ *                                        sweeps, flags (FMCW_MUSIC_FB = 1), src_thr; cov: real single (2*T) x (Nr*F),
+ *                                        T = A (A + 1) / 2, A in 2..8; nr: the rows of one frame; w as for 'ra';
+ *                                        music is K x (Nr*F) single (reshape(music, K, Nr, F)), nsrc 1 x (Nr*F) int32,
+ *                                        eval A x (Nr*F) single (ascending), evec (2*A*A) x (Nr*F) single
+ *                                        (reshape(evec, 2, A, A, Nr, F): re and im; component; eigenvector), music_max
+ *                                        a double
  *   fmcw_mex('close')                                            -> fmcw_ctx_destroy
  *
  * P is a struct with the fields of fmcw_params (nts, pn, nr, nd, max_targets,
@@ -703,6 +714,52 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     check(fmcw_ra(g_ctx, &q, chan, FMCW_C64, F, nr, nd, wf, mxGetSingles(cov), mxGetSingles(plhs[0]), &mx));
     if (nlhs > 1) plhs[1] = cov;
     if (nlhs > 2) plhs[2] = mxCreateDoubleScalar((double)mx);
+    return;
+  }
+  if (!strcmp(cmd, "music")) {              /* [music, nsrc, eval, evec, music_max] = fmcw_mex('music', Q, cov, nr, w) */
+    if (nrhs != 5) mexErrMsgIdAndTxt("fmcw:arg", "music: Q, cov, nr, w");
+    const mxArray* s = prhs[1];
+    const mxArray* cov = prhs[2];
+    const mxArray* w = prhs[4];
+    if (!mxIsStruct(s)) mexErrMsgIdAndTxt("fmcw:arg", "Q must be a struct");
+    if (!mxIsSingle(cov) || mxIsComplex(cov) || mxGetNumberOfDimensions(cov) != 2)
+      mexErrMsgIdAndTxt("fmcw:arg", "cov must be real single (2*T) x (Nr*F)");
+    mwSize A = 0;
+    for (mwSize a = 2; a <= 8; ++a)
+      if (mxGetM(cov) == a * (a + 1)) A = a;
+    const int32_t nr = (int32_t)mxGetScalar(prhs[3]);
+    if (A == 0 || nr < 1 || mxGetN(cov) % (mwSize)nr)
+      mexErrMsgIdAndTxt("fmcw:arg", "cov must have A (A + 1) rows, A in 2..8, and a multiple of nr columns");
+    const int64_t F = (int64_t)(mxGetN(cov) / (mwSize)nr);
+    if (!mxIsDouble(w) || mxIsComplex(w) || mxGetNumberOfElements(w) == 0 || mxGetNumberOfElements(w) % (2 * A) ||
+        mxGetNumberOfElements(w) > 512 * A)
+      mexErrMsgIdAndTxt("fmcw:arg", "w must be a real double array of 2 x A x K values (re, im; plane; direction), K in 1..256");
+    fmcw_music_params q;
+    memset(&q, 0, sizeof q);
+    q.n_chan = (int32_t)A;
+    q.n_ang = (int32_t)(mxGetNumberOfElements(w) / (2 * A));
+    q.r_lo = (int32_t)field(s, "r_lo");
+    q.r_hi = (int32_t)field(s, "r_hi");
+    q.n_src = (int32_t)field(s, "n_src");
+    q.max_src = (int32_t)field(s, "max_src");
+    q.sweeps = (int32_t)field(s, "sweeps");
+    q.flags = (int32_t)field(s, "flags");
+    q.src_thr = (float)field(s, "src_thr");
+    check(fmcw_music_check(&q, nr));
+    float* wf = (float*)mxCalloc(mxGetNumberOfElements(w), sizeof(float));   /* freed with the MEX call's memory */
+    for (mwSize i = 0; i < mxGetNumberOfElements(w); ++i) wf[i] = (float)mxGetDoubles(w)[i];
+    const mwSize rows = mxGetN(cov);
+    plhs[0] = mxCreateNumericMatrix((mwSize)q.n_ang, rows, mxSINGLE_CLASS, mxREAL);
+    mxArray* nsrc = mxCreateNumericMatrix(1, rows, mxINT32_CLASS, mxREAL);
+    mxArray* eval = mxCreateNumericMatrix(A, rows, mxSINGLE_CLASS, mxREAL);
+    mxArray* evec = mxCreateNumericMatrix(2 * A * A, rows, mxSINGLE_CLASS, mxREAL);
+    float mx = 0.f;
+    check(fmcw_music(g_ctx, &q, mxGetSingles(cov), F, nr, wf, mxGetSingles(eval), mxGetSingles(evec), mxGetInt32s(nsrc),
+                     mxGetSingles(plhs[0]), &mx));
+    if (nlhs > 1) plhs[1] = nsrc;
+    if (nlhs > 2) plhs[2] = eval;
+    if (nlhs > 3) plhs[3] = evec;
+    if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)mx);
     return;
   }
   mexErrMsgIdAndTxt("fmcw:arg", "unknown command '%s'", cmd);
