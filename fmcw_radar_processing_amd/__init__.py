@@ -6,9 +6,9 @@ imported from here.
 """
 from ._lib import (FMCW_C32H, FMCW_C64, FMCW_PIPE_AUTO, FMCW_PIPE_ONEPASS, FMCW_PIPE_STREAMS, FMCW_PIPE_XCD,  # noqa: F401
                    FmcwError)
-from .params import FmcwConfig, MusicConfig, RaConfig, calibration, config, derive_params, deployed_device  # noqa: F401
+from .params import DoaConfig, FmcwConfig, MusicConfig, RaConfig, calibration, config, derive_params, deployed_device  # noqa: F401
 
-__all__ = ["Engine", "FmcwConfig", "FmcwError", "RaConfig", "calibration", "config", "derive_params",
+__all__ = ["DoaConfig", "Engine", "FmcwConfig", "FmcwError", "MusicConfig", "RaConfig", "calibration", "config", "derive_params",
            "deployed_device", "radar_processing"]
 
 

@@ -22,12 +22,14 @@ STATUS_NAMES = {0: "OK", -1: "E_ARG", -2: "E_HIP", -3: "E_OOM", -4: "E_STATE", -
 STAGES = ("range", "doppler", "detect", "compact", "stft_power", "stft_db", "range_only", "range_doppler", "onepass",
           "render", "cfar", "cluster", "track", "mti", "aoa", "beam", "oscfar", "ra")
 MUSIC_STAGE = 18           # fmcw_timing_read's stage of fmcw_music_device ("music" in Engine.timing_read)
+DOA_STAGE = 19             # fmcw_timing_read_ext's stage of fmcw_doa_device ("doa" in Engine.timing_read)
 FMCW_CFAR_LOCAL_MAX = 1
 FMCW_SIG_DB = 1
 FMCW_MTI_RAMP, FMCW_MTI_FREEZE = 1, 2
 FMCW_BEAM_NCI = 1
 FMCW_RA_CAPON = 1
 FMCW_MUSIC_FB = 1
+FMCW_DOA_EDGES, FMCW_DOA_WRAP, FMCW_DOA_INV = 1, 2, 4
 
 
 class FmcwError(RuntimeError):
@@ -141,6 +143,12 @@ class MusicParams(ct.Structure):
                 ("src_thr", ct.c_float)]
 
 
+class DoaParams(ct.Structure):
+    """fmcw_doa_params (include/fmcw.h)."""
+    _fields_ = [("n_ang", ct.c_int32), ("r_lo", ct.c_int32), ("r_hi", ct.c_int32), ("max_pk", ct.c_int32),
+                ("flags", ct.c_int32), ("min_abs", ct.c_float), ("min_rel", ct.c_float), ("min_prom", ct.c_float)]
+
+
 class JsonField(ct.Structure):
     """fmcw_json_field (include/fmcw.h)."""
     _fields_ = [("name", ct.c_char_p), ("kind", ct.c_int32), ("data", ct.c_void_p),
@@ -234,6 +242,10 @@ SIGNATURES = {
     "fmcw_music_check": (ct.c_int, [ct.POINTER(MusicParams), _I32]),
     "fmcw_music_device": (ct.c_int, [_P, ct.POINTER(MusicParams), _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "fmcw_music": (ct.c_int, [_P, ct.POINTER(MusicParams), _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
+    "fmcw_doa_check": (ct.c_int, [ct.POINTER(DoaParams), _I32]),
+    "fmcw_doa_device": (ct.c_int, [_P, ct.POINTER(DoaParams), _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "fmcw_doa": (ct.c_int, [_P, ct.POINTER(DoaParams), _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
+    "fmcw_timing_read_ext": (ct.c_int, [_P, _I32, ct.POINTER(_D), ct.POINTER(_I64)]),
     "fmcw_json_write": (ct.c_int, [ct.c_char_p, ct.POINTER(JsonField), _I32, _I32, _I32, ct.POINTER(_I64)]),
     "fmcw_stft_png": (ct.c_int, [_P, _P, _I64, _P, _I32, _I32, _I32, _D, _I32, _P, _P, _P, ct.c_char_p, _I32, _I32,
                                  ct.POINTER(_I64)]),

@@ -127,7 +127,8 @@ inline void shard(int64_t total, int g, int world, int64_t& f0, int64_t& n) {
   n = base + (g < rem ? 1 : 0);
 }
 
-constexpr int kStages = 19;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar, 11 cluster, 12 track, 13 mti, 14 aoa, 15 beam, 16 oscfar, 17 ra, 18 music
+constexpr int kStages = 20;  // 0..6 per kernel (see fmcw.h), 7 range+Doppler span per call, 8 k_rdx, 9 render, 10 cfar, 11 cluster, 12 track, 13 mti, 14 aoa, 15 beam, 16 oscfar, 17 ra, 18 music, 19 doa
+constexpr int kStagesRead = 19;  // fmcw_timing_read answers for 0..18 only (fmcw.h); fmcw_timing_read_ext for all
 
 }  // namespace fmcw
 
@@ -270,6 +271,8 @@ struct fmcw_ctx {
   // fmcw_music (host pointers): the chunk's covariances, its four outputs, and the weight table with the
   // running maximum on the device
   DevBuf mu_cov, mu_eval, mu_evec, mu_nsrc, mu_out, mu_w;
+  // fmcw_doa (host pointers): the chunk's spectra, the grid and the chunk's five outputs
+  DevBuf doa_spec, doa_u, doa_count, doa_idx, doa_pow, doa_sin, doa_base;
   int64_t chunk_frames = 0;
   int64_t last_coarse_tiles = -1;     // tiles the last coarse-to-fine max(P) evaluated in full (diagnostics)
   int pipe_mode = FMCW_PIPE_AUTO;

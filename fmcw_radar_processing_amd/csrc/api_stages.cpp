@@ -1576,4 +1576,112 @@ int fmcw_music(fmcw_ctx* c, const fmcw_music_params* q, const float* cov, int64_
   return FMCW_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Directions of arrival: per range row the peaks of its angular spectrum (kernels_doa.hip)
+// ---------------------------------------------------------------------------
+int fmcw_doa_check(const fmcw_doa_params* q, int32_t nr) {
+  if (!q) return fail(FMCW_E_ARG, "doa params is NULL");
+  CHK(check_rd_shape("doa", nr, 4));
+  CHK(check_gate("doa", q->r_lo, q->r_hi, nr));
+  if (q->n_ang < 1 || q->n_ang > fmcw::kRaAngMax) return fail(FMCW_E_ARG, "doa: n_ang must be in [1, 256]");
+  if (q->max_pk < 1 || q->max_pk > fmcw::kDoaPkMax) return fail(FMCW_E_ARG, "doa: max_pk must be in [1, 8]");
+  if (q->flags & ~(FMCW_DOA_EDGES | FMCW_DOA_WRAP | FMCW_DOA_INV)) return fail(FMCW_E_ARG, "doa: unknown flag bits");
+  if ((q->flags & FMCW_DOA_EDGES) && (q->flags & FMCW_DOA_WRAP))
+    return fail(FMCW_E_ARG, "doa: FMCW_DOA_EDGES and FMCW_DOA_WRAP exclude each other");
+  if ((q->flags & FMCW_DOA_WRAP) && q->n_ang < 3) return fail(FMCW_E_ARG, "doa: FMCW_DOA_WRAP needs n_ang >= 3");
+  if (!(std::isfinite(q->min_abs) && q->min_abs >= 0.f)) return fail(FMCW_E_ARG, "doa: min_abs must be finite and >= 0");
+  if (!(q->min_rel >= 0.f && q->min_rel <= 1.f)) return fail(FMCW_E_ARG, "doa: min_rel must be in [0, 1]");
+  if (!(std::isfinite(q->min_prom) && q->min_prom >= 0.f)) return fail(FMCW_E_ARG, "doa: min_prom must be finite and >= 0");
+  return FMCW_OK;
+}
+
+static int doa_entry(fmcw_ctx* c, const fmcw_doa_params* q, int64_t F, int32_t nr) {
+  if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
+  CHK(fmcw_doa_check(q, nr));
+  if (F < 0) return fail(FMCW_E_ARG, "F < 0");
+  if (F > ((int64_t)1 << 40)) return fail(FMCW_E_ARG, "doa: F must be at most 2^40");
+  return FMCW_OK;
+}
+
+int fmcw_doa_device(fmcw_ctx* c, const fmcw_doa_params* q, const float* d_spec, int64_t F, int32_t nr, const float* d_sin_theta,
+                    int32_t* d_count, int32_t* d_idx, float* d_pow, float* d_sin, float* d_base, void* stream) {
+  CHK(doa_entry(c, q, F, nr));
+  if (!d_count && !d_idx && !d_pow && !d_sin && !d_base) return fail(FMCW_E_ARG, "doa: every output is NULL");
+  if (F == 0) return FMCW_OK;
+  if (!d_spec || !d_sin_theta) return fail(FMCW_E_ARG, "required pointer is NULL");
+  if ((reinterpret_cast<uintptr_t>(d_spec) | reinterpret_cast<uintptr_t>(d_sin_theta) | reinterpret_cast<uintptr_t>(d_count) |
+       reinterpret_cast<uintptr_t>(d_idx) | reinterpret_cast<uintptr_t>(d_pow) | reinterpret_cast<uintptr_t>(d_sin) |
+       reinterpret_cast<uintptr_t>(d_base)) & 15)
+    return fail(FMCW_E_ARG, "doa: d_spec, d_sin_theta, d_count, d_idx, d_pow, d_sin and d_base must be 16-byte aligned");
+  CHK(set_device(c));
+  hipStream_t s = pick(c, stream);
+  fmcw::DoaArgs a{};
+  a.K = q->n_ang; a.NR = nr; a.max_pk = q->max_pk; a.flags = q->flags;
+  gate_rows(q->r_lo, q->r_hi, nr, a.g0, a.g1);
+  a.min_abs = q->min_abs; a.min_rel = q->min_rel; a.min_prom = q->min_prom;
+  a.u = d_sin_theta;
+  // at most kRaRowsMax rows per launch (the results do not depend on the cut)
+  const int64_t Fc = fmcw::kRaRowsMax / nr;
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    a.rows = std::min(Fc, F - f0) * nr;
+    const int64_t r0 = f0 * nr;
+    a.spec = d_spec + r0 * a.K;
+    a.count = shifted(d_count, r0);
+    a.idx = shifted(d_idx, r0 * a.max_pk);
+    a.pw = shifted(d_pow, r0 * a.max_pk);
+    a.sn = shifted(d_sin, r0 * a.max_pk);
+    a.base = shifted(d_base, r0 * a.max_pk);
+    StageTimer tm(c, 19, s);
+    HIPCHK(fmcw::launch_doa(a, s));
+    tm.done();
+  }
+  return FMCW_OK;
+}
+
+// One shard of fmcw_doa, chunk by chunk: the chunk's spectra in, what was asked for out.
+static int doa_host_one(fmcw_ctx* c, const fmcw_doa_params* q, const float* spec, int64_t F, int32_t nr, const float* u,
+                        int32_t* count, int32_t* idx, float* pw, float* sn, float* base) {
+  CHK(set_device(c));
+  hipStream_t s = c->stream;
+  const size_t K = (size_t)q->n_ang, P = (size_t)q->max_pk;
+  const size_t specf = (size_t)nr * K, pkf = (size_t)nr * P;            // per frame
+  const int64_t Fc = c->chunk_frames > 0 ? std::min<int64_t>(c->chunk_frames, F) : host_chunk(specf * 4, F);
+  CHK(c->doa_spec.ensure((size_t)Fc * specf * 4));
+  CHK(c->doa_u.ensure(K * 4));
+  if (count) CHK(c->doa_count.ensure((size_t)Fc * nr * 4));
+  if (idx) CHK(c->doa_idx.ensure((size_t)Fc * pkf * 4));
+  if (pw) CHK(c->doa_pow.ensure((size_t)Fc * pkf * 4));
+  if (sn) CHK(c->doa_sin.ensure((size_t)Fc * pkf * 4));
+  if (base) CHK(c->doa_base.ensure((size_t)Fc * pkf * 4));
+  HIPCHK(hipMemcpyAsync(c->doa_u.p, u, K * 4, hipMemcpyHostToDevice, s));
+  for (int64_t f0 = 0; f0 < F; f0 += Fc) {
+    const int64_t nf = std::min(Fc, F - f0);
+    HIPCHK(hipMemcpyAsync(c->doa_spec.p, spec + (size_t)f0 * specf, (size_t)nf * specf * 4, hipMemcpyHostToDevice, s));
+    CHK(fmcw_doa_device(c, q, c->doa_spec.as<float>(), nf, nr, c->doa_u.as<float>(), count ? c->doa_count.as<int32_t>() : nullptr,
+                        idx ? c->doa_idx.as<int32_t>() : nullptr, pw ? c->doa_pow.as<float>() : nullptr,
+                        sn ? c->doa_sin.as<float>() : nullptr, base ? c->doa_base.as<float>() : nullptr, s));
+    if (count) HIPCHK(hipMemcpyAsync(count + (size_t)f0 * nr, c->doa_count.p, (size_t)nf * nr * 4, hipMemcpyDeviceToHost, s));
+    if (idx) HIPCHK(hipMemcpyAsync(idx + (size_t)f0 * pkf, c->doa_idx.p, (size_t)nf * pkf * 4, hipMemcpyDeviceToHost, s));
+    if (pw) HIPCHK(hipMemcpyAsync(pw + (size_t)f0 * pkf, c->doa_pow.p, (size_t)nf * pkf * 4, hipMemcpyDeviceToHost, s));
+    if (sn) HIPCHK(hipMemcpyAsync(sn + (size_t)f0 * pkf, c->doa_sin.p, (size_t)nf * pkf * 4, hipMemcpyDeviceToHost, s));
+    if (base) HIPCHK(hipMemcpyAsync(base + (size_t)f0 * pkf, c->doa_base.p, (size_t)nf * pkf * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));           // the chunk buffers are reused by the next chunk
+  }
+  return FMCW_OK;
+}
+
+int fmcw_doa(fmcw_ctx* c, const fmcw_doa_params* q, const float* spec, int64_t F, int32_t nr, const float* sin_theta,
+             int32_t* count, int32_t* idx, float* pw, float* sn, float* base) {
+  CHK(doa_entry(c, q, F, nr));
+  if (!count && !idx && !pw && !sn && !base) return fail(FMCW_E_ARG, "doa: every output is NULL");
+  if (F == 0) return FMCW_OK;
+  if (!spec || !sin_theta) return fail(FMCW_E_ARG, "required pointer is NULL");
+  const int64_t specf = (int64_t)nr * q->n_ang, pkf = (int64_t)nr * q->max_pk;
+  // frames are independent: contiguous shards, each written in place
+  return over_devices(c, F, [&](fmcw_ctx* d, int, int64_t f0, int64_t n) {
+    return doa_host_one(d, q, spec + f0 * specf, n, nr, sin_theta, shifted(count, f0 * nr), shifted(idx, f0 * pkf),
+                        shifted(pw, f0 * pkf), shifted(sn, f0 * pkf), shifted(base, f0 * pkf));
+  });
+}
+
 }  // extern "C"

@@ -455,14 +455,22 @@ static int timing_collect(fmcw_ctx* c) {
   return FMCW_OK;
 }
 
-int fmcw_timing_read(fmcw_ctx* c, int32_t stage, double* total_ms, int64_t* launches) {
+static int timing_read(fmcw_ctx* c, int32_t stage, int32_t stages, double* total_ms, int64_t* launches) {
   if (!c) return fail(FMCW_E_ARG, "ctx is NULL");
-  if (stage < 0 || stage >= kStages) return fail(FMCW_E_ARG, "stage out of range");
+  if (stage < 0 || stage >= stages) return fail(FMCW_E_ARG, "stage out of range");
   CHK(set_device(c));
   CHK(timing_collect(c));
   if (total_ms) *total_ms = c->total_ms[stage];
   if (launches) *launches = c->launches[stage];
   return FMCW_OK;
+}
+
+int fmcw_timing_read(fmcw_ctx* c, int32_t stage, double* total_ms, int64_t* launches) {
+  return timing_read(c, stage, kStagesRead, total_ms, launches);
+}
+
+int fmcw_timing_read_ext(fmcw_ctx* c, int32_t stage, double* total_ms, int64_t* launches) {
+  return timing_read(c, stage, kStages, total_ms, launches);
 }
 
 int fmcw_timing_reset(fmcw_ctx* c) {

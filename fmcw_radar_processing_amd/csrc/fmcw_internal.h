@@ -499,6 +499,26 @@ struct MusicArgs {
 };
 hipError_t launch_music(const MusicArgs& a, hipStream_t s);
 
+// Directions of arrival (kernels_doa.hip): k_doa (per range row the peaks of its angular spectrum,
+// thinned, ordered by power, each with a sub-grid direction)
+constexpr int kDoaPkMax = 8;           // written peaks of a row at most
+struct DoaArgs {
+  const float* spec;               // [rows][K]
+  const float* u;                  // [K]: the grid, sin(theta) of every look direction
+  int32_t* count;                  // [rows] or nullptr
+  int32_t* idx;                    // [rows][max_pk] or nullptr
+  float* pw;                       // [rows][max_pk] or nullptr
+  float* sn;                       // [rows][max_pk] or nullptr
+  float* base;                     // [rows][max_pk] or nullptr
+  int64_t rows;
+  int K, NR;
+  int g0, g1;
+  int max_pk;
+  int flags;                       // FMCW_DOA_*
+  float min_abs, min_rel, min_prom;
+};
+hipError_t launch_doa(const DoaArgs& a, hipStream_t s);
+
 bool range_size_supported(int nr);
 bool doppler_size_supported(int nd);
 

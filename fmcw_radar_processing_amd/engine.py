@@ -16,9 +16,9 @@ import ctypes as ct
 import numpy as np
 
 from . import _lib
-from ._lib import FMCW_C32H, FMCW_C64, MUSIC_STAGE, STAGES, FmcwError, check
-from .params import (AoaConfig, BeamConfig, CfarConfig, ClusterConfig, FmcwConfig, MtiConfig, MusicConfig, OsCfarConfig, RaConfig,
-                     SigConfig, TrackConfig)
+from ._lib import DOA_STAGE, FMCW_C32H, FMCW_C64, MUSIC_STAGE, STAGES, FmcwError, check
+from .params import (AoaConfig, BeamConfig, CfarConfig, ClusterConfig, DoaConfig, FmcwConfig, MtiConfig, MusicConfig, OsCfarConfig,
+                     RaConfig, SigConfig, TrackConfig)
 
 
 def _ptr(a) -> ct.c_void_p:
@@ -880,6 +880,53 @@ class Engine:
         return {"cov": d_cov.cpu().numpy(), "eval": d_eval.cpu().numpy(), "evec": d_evec.cpu().numpy(),
                 "nsrc": d_nsrc.cpu().numpy(), "music": d_music.cpu().numpy(), "music_max": float(d_mx.cpu()[0])}
 
+    # ---- directions of arrival: the peaks of the angular spectra per range row (fmcw_doa_params) ----
+    def doa_device(self, q: DoaConfig, d_spec, F: int, nr: int, d_sin, d_count=None, d_idx=None, d_pow=None, d_sin_out=None,
+                   d_base=None, stream=None) -> None:
+        """fmcw_doa_device: d_spec float32 [F][nr][q.n_ang] (of ra_device or music_device, or the
+        caller's own); d_sin float32 [q.n_ang], the grid the weight table was formed on; d_count int32
+        [F][nr], d_idx int32 [F][nr][q.max_pk], d_pow, d_sin_out, d_base float32 [F][nr][q.max_pk], any
+        of them None but not all.  q: a DoaConfig, or the C struct _lib.DoaParams itself.
+        Asynchronous on `stream`."""
+        qa = q.to_c() if hasattr(q, "to_c") else q
+        with _sided(stream) as hs:
+            check(self.lib.fmcw_doa_device(self.h, ct.byref(qa), _ptr(d_spec), int(F), int(nr), _ptr(d_sin), _ptr(d_count),
+                                           _ptr(d_idx), _ptr(d_pow), _ptr(d_sin_out), _ptr(d_base), hs))
+
+    def doa(self, spec, q: DoaConfig, sin_theta, want=("count", "idx", "pow", "sin", "base")) -> dict:
+        """fmcw_doa on a host spectrum float32 [F][nr][q.n_ang] and the grid sin_theta [q.n_ang]:
+        dict(count, idx, pow, sin, base) with None for what `want` leaves out.  Frames sharded over
+        the context's devices."""
+        spec = np.ascontiguousarray(spec, np.float32)
+        u = np.ascontiguousarray(sin_theta, np.float32)
+        K, P = int(q.n_ang), int(q.max_pk)
+        if spec.ndim != 3 or spec.shape[2] != K:
+            raise ValueError("doa: spec must be [F][nr][n_ang]")
+        if u.shape != (K,):
+            raise ValueError("doa: sin_theta must be [n_ang]")
+        F, nr = spec.shape[:2]
+        out = {"count": np.empty((F, nr), np.int32) if "count" in want else None,
+               "idx": np.empty((F, nr, P), np.int32) if "idx" in want else None}
+        for k in ("pow", "sin", "base"):
+            out[k] = np.empty((F, nr, P), np.float32) if k in want else None
+        qa = q.to_c() if hasattr(q, "to_c") else q
+        check(self.lib.fmcw_doa(self.h, ct.byref(qa), _ptr(spec), F, nr, _ptr(u), _ptr(out["count"]), _ptr(out["idx"]),
+                                _ptr(out["pow"]), _ptr(out["sin"]), _ptr(out["base"])))
+        return out
+
+    @staticmethod
+    def doa_positions(out: dict, range_m) -> tuple:
+        """(x, y) float64 [F][nr][max_pk] of the written peaks of a doa result (its idx and sin) with
+        the rows' ranges range_m [nr] in metres: x = R sin, y = R sqrt(1 - sin^2) (NaN where |sin| > 1);
+        NaN in unused slots.  Host-side numpy, not held bit-exact."""
+        sn = np.asarray(out["sin"], np.float64)
+        R = np.asarray(range_m, np.float64).reshape(1, -1, 1)
+        used = np.asarray(out["idx"]) >= 0
+        with np.errstate(invalid="ignore"):
+            x = np.where(used, R * sn, np.nan)
+            y = np.where(used, R * np.sqrt(1.0 - sn * sn), np.nan)
+        return x, y
+
     # ---- timing -----------------------------------------------------------------
     def timing(self, level: int) -> None:
         """0 off, 1 per range+Doppler chunk + STFT launches, 2 per kernel launch, 3 the dominant
@@ -891,9 +938,9 @@ class Engine:
 
     def timing_read(self) -> dict:
         out = {}
-        for i, name in list(enumerate(STAGES)) + [(MUSIC_STAGE, "music")]:
+        for i, name in list(enumerate(STAGES)) + [(MUSIC_STAGE, "music"), (DOA_STAGE, "doa")]:
             ms, n = ct.c_double(), ct.c_int64()
-            check(self.lib.fmcw_timing_read(self.h, i, ct.byref(ms), ct.byref(n)))
+            check(self.lib.fmcw_timing_read_ext(self.h, i, ct.byref(ms), ct.byref(n)))
             out[name] = (ms.value, n.value)
         return out
 

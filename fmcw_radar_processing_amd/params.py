@@ -12,8 +12,9 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import windows
-from ._lib import (FMCW_BEAM_NCI, FMCW_CFAR_LOCAL_MAX, FMCW_MTI_FREEZE, FMCW_MTI_RAMP, FMCW_MUSIC_FB, FMCW_RA_CAPON, FMCW_SIG_DB,
-                   AoaParams, BeamParams, CfarParams, ClusterParams, MtiParams, MusicParams, OsCfarParams, Params, RaParams, SigParams, TrackParams)
+from ._lib import (FMCW_BEAM_NCI, FMCW_CFAR_LOCAL_MAX, FMCW_DOA_EDGES, FMCW_DOA_INV, FMCW_DOA_WRAP, FMCW_MTI_FREEZE, FMCW_MTI_RAMP,
+                   FMCW_MUSIC_FB, FMCW_RA_CAPON, FMCW_SIG_DB, AoaParams, BeamParams, CfarParams, ClusterParams, DoaParams, MtiParams,
+                   MusicParams, OsCfarParams, Params, RaParams, SigParams, TrackParams)
 
 C0 = 3e8  # radar_processing.m:67
 
@@ -693,3 +694,64 @@ class MusicConfig:
             thr = np.float32(self.src_thr)
         if not (np.isfinite(thr) and thr > 0):
             raise ValueError("music: src_thr must be finite and > 0")
+
+
+@dataclass
+class DoaConfig:
+    """fmcw_doa_params (include/fmcw.h): directions of arrival, the peaks of an angular spectrum
+    [F][nr][n_ang] (Bartlett or Capon of RaConfig, MUSIC of MusicConfig, or a caller's own) per range
+    row.  A peak is above both neighbours (of a flat top its first point); it is kept when positive,
+    >= min_abs, >= min_rel times the row's maximum and >= min_prom times its base (the reference
+    level of findpeaks' prominence; 0 switches the rule off); kept peaks are ordered by power and
+    the first max_pk written, each with a sub-grid direction from a parabola through the peak and
+    its neighbours (inv: through their reciprocals, for Capon and MUSIC).  edges: the first and
+    the last grid point can be peaks; wrap: the grid is cyclic (not with edges; n_ang >= 3).  The
+    gate r_lo..r_hi is 1-based and inclusive, (0, 0) = every row; rows outside it hold no peak."""
+    n_ang: int
+    max_pk: int = 4
+    r_lo: int = 0
+    r_hi: int = 0
+    edges: bool = False
+    wrap: bool = False
+    inv: bool = False
+    min_abs: float = 0.0
+    min_rel: float = 0.0
+    min_prom: float = 0.0
+
+    @property
+    def flags(self) -> int:
+        return (FMCW_DOA_EDGES if self.edges else 0) | (FMCW_DOA_WRAP if self.wrap else 0) | (FMCW_DOA_INV if self.inv else 0)
+
+    def to_c(self) -> DoaParams:
+        return DoaParams(int(self.n_ang), int(self.r_lo), int(self.r_hi), int(self.max_pk), self.flags, self.min_abs,
+                         self.min_rel, self.min_prom)
+
+    abi = to_c                  # the name the other configurations use
+
+    def check(self, nr: int) -> None:
+        """The rules of fmcw_doa_check, on the float32 values the C struct carries; ValueError
+        naming the first one violated."""
+        if nr < 16 or nr > 2048 or nr & (nr - 1):
+            raise ValueError("doa: nr must be a power of two in [16, 2048]")
+        if self.r_lo > self.r_hi:
+            raise ValueError("doa: r_lo > r_hi")
+        if (self.r_lo, self.r_hi) != (0, 0) and (self.r_lo < 1 or self.r_hi > nr):
+            raise ValueError("doa: the gate r_lo..r_hi must lie in 1..nr (or be 0, 0 for all rows)")
+        if not 1 <= self.n_ang <= 256:
+            raise ValueError("doa: n_ang must be in [1, 256]")
+        if not 1 <= self.max_pk <= 8:
+            raise ValueError("doa: max_pk must be in [1, 8]")
+        if self.edges and self.wrap:
+            raise ValueError("doa: FMCW_DOA_EDGES and FMCW_DOA_WRAP exclude each other")
+        if self.wrap and self.n_ang < 3:
+            raise ValueError("doa: FMCW_DOA_WRAP needs n_ang >= 3")
+        with np.errstate(over="ignore"):
+            min_abs, min_rel, min_prom = np.float32(self.min_abs), np.float32(self.min_rel), np.float32(self.min_prom)
+        if not (np.isfinite(min_abs) and min_abs >= 0):
+            raise ValueError("doa: min_abs must be finite and >= 0")
+        if not 0 <= min_rel <= 1:
+            raise ValueError("doa: min_rel must be in [0, 1]")
+        if not (np.isfinite(min_prom) and min_prom >= 0):
+            raise ValueError("doa: min_prom must be finite and >= 0")
+
+    validate = check            # the name the other configurations use

@@ -62,7 +62,10 @@ extern "C" {
  *    + the range-angle entry points (fmcw_ra_check, fmcw_ra_steer, fmcw_cov_device, fmcw_ra_device,
  *    fmcw_ra), the struct fmcw_ra_params and timing stage 17, added within ABI 4 in the same way
  *    + the MUSIC entry points (fmcw_music_check, fmcw_music_device, fmcw_music), the struct
- *    fmcw_music_params and timing stage 18, added within ABI 4 in the same way */
+ *    fmcw_music_params and timing stage 18, added within ABI 4 in the same way
+ *    + the direction-of-arrival entry points (fmcw_doa_check, fmcw_doa_device, fmcw_doa), the struct
+ *    fmcw_doa_params, timing stage 19 and its reader fmcw_timing_read_ext, added within ABI 4 in the
+ *    same way */
 #define FMCW_ABI_VERSION 4
 
 typedef enum fmcw_status {
@@ -298,10 +301,13 @@ int fmcw_synth_device(fmcw_ctx* ctx, const fmcw_params* p, int64_t frame0, int64
  *        fmcw_beam_device), 16 oscfar (one pair per k_oscfar + k_cfar_gather + k_oscfar_select
  *        launch group of fmcw_oscfar_device), 17 ra (one pair per k_cov launch of fmcw_cov_device
  *        and one per k_ra launch of fmcw_ra_device), 18 music (one pair per k_music launch of
- *        fmcw_music_device).
- *        fmcw_timing_read synchronises. */
+ *        fmcw_music_device), 19 doa (one pair per k_doa launch of fmcw_doa_device).
+ *        fmcw_timing_read synchronises.  It answers for the stages 0..18 and keeps returning FMCW_E_ARG
+ *        for any other, 19 included: callers written against stage 18 as the last one see no change.
+ *        fmcw_timing_read_ext is the same call for every stage, 0..19.  fmcw_timing_reset clears all. */
 int fmcw_timing_enable(fmcw_ctx* ctx, int32_t enable);
 int fmcw_timing_read(fmcw_ctx* ctx, int32_t stage, double* total_ms, int64_t* launches);
+int fmcw_timing_read_ext(fmcw_ctx* ctx, int32_t stage, double* total_ms, int64_t* launches);
 int fmcw_timing_reset(fmcw_ctx* ctx);
 
 /* Frames per range/Doppler chunk of the 3-stream pipeline (the range cube of
@@ -1179,6 +1185,92 @@ int fmcw_music_device(fmcw_ctx* ctx, const fmcw_music_params* q, const float* d_
  * maximum over all shards, 0 without music. */
 int fmcw_music(fmcw_ctx* ctx, const fmcw_music_params* q, const float* cov, int64_t F, int32_t nr, const float* w,
                float* eval, float* evec, int32_t* nsrc, float* music, float* music_max);
+
+/* ---------------------------------------------------------------------------
+ * Directions of arrival: the peaks of an angular spectrum per range row, thinned, ordered by power,
+ * each with a sub-grid direction (added within ABI 4; beyond the reference).  fmcw_ra* and
+ * fmcw_music* end in a spectrum [F][nr][n_ang]; this stage turns it into what a caller wants from
+ * it: how many returns a row holds, in which directions and how strong, as a fixed-size record per
+ * row in the form of the CFAR lists.
+ *   Input: spec [F][nr][K] float32, K = n_ang in 1..256: what fmcw_ra_device or fmcw_music_device
+ *     wrote, or a caller's own spectrum; sin_theta [K] float32, the grid u the weight table was
+ *     formed on (the table does not carry it); nr within CFAR's limits.
+ *   Outputs; unused slots and every row outside the gate r_lo..r_hi hold idx -1, floats +0, count 0:
+ *     count [F][nr] int32          the peaks kept; it may exceed max_pk (as CFAR's count may max_det);
+ *     idx   [F][nr][max_pk] int32  the grid point k of every written peak;
+ *     pow, sin, base [F][nr][max_pk] float32: s[k], the sub-grid direction, the peak's reference level.
+ *   Everything is float32, every operation rounded on its own in the order written (no fused
+ *   multiply-add), divides correctly rounded: every output byte equals the plain-loop evaluation of
+ *   the steps below (tests/doa_reference.py) on the same bytes, for any F and any sharding or
+ *   chunking, and does not depend on which other outputs were asked for.  Per gated row s[0..K-1]:
+ *   0. Extremes.  hi = max s, lo = min s, by compares.  Unless hi > lo and hi > 0 the row has no peak.
+ *   1. Peak test.  For k let L = k - 1 and R the first index right of k with s[R] != s[k]; k is a
+ *      peak iff s[L] < s[k] and s[R] < s[k]: of a flat top only its first point qualifies, and a
+ *      flat stretch that then rises is no peak.  Default: if L or R does not exist (k = 0, or the
+ *      walk reaches the end) k is no peak, as MATLAB's findpeaks treats end points.
+ *      FMCW_DOA_EDGES: a missing neighbour counts as lower.  FMCW_DOA_WRAP: indices are taken modulo
+ *      K (hi > lo: R exists).
+ *   2. Base, the reference level of findpeaks' prominence.  Walk left from k over the indices j with
+ *      s[j] <= s[k]; stop before the first s[j] > s[k], or at the end, or after K - 1 steps under
+ *      WRAP.  lmin: the minimum over the visited j (k itself is not among them); rmin the same to the
+ *      right; base = max(lmin, rmin) + 0.0f (a zero base is +0).  A side with nothing visited does
+ *      not take part (only at an end under EDGES).
+ *   3. Keep k iff s[k] > 0 and s[k] >= min_abs and s[k] >= fl(min_rel hi) and s[k] >= fl(min_prom
+ *      base).  The prominence rule is a ratio because MUSIC's pseudo-spectrum has no absolute scale;
+ *      min_prom = 0 switches it off.
+ *   4. Order.  Kept peaks by descending s[k], ties by ascending k; count = the number kept; the first
+ *      max_pk are written: pow = s[k], base as above.
+ *   5. Sub-grid direction of every written peak.  kl = k - 1, kr = k + 1, modulo K under WRAP.  If a
+ *      neighbour is missing sin = u[k], the grid value itself.  Otherwise (l, c, r) = (s[kl], s[k],
+ *      s[kr]) and delta = 0; with FMCW_DOA_INV the parabola is laid through the reciprocals, which
+ *      suits Capon and MUSIC (one over a quadratic form that is smooth at its minimum): if l > 0 and
+ *      r > 0 the three become 1/l, 1/c, 1/r, otherwise delta stays 0 and the next line is skipped.
+ *        den = (l - c) + (r - c);  num = 0.5f (l - r);  delta = num / den when den is finite and
+ *        not 0 and num is finite.
+ *      delta is then clamped to [-0.5, 0.5] (in exact arithmetic a peak's |delta| is at most 0.5; the
+ *      halving in num rounds when l - r is an odd number of denormal units, e.g. 0.5f * 3u = 2u over
+ *      den = 3u).  delta >= 0: sin = u[k] + delta (u[kr] - u[k]);
+ *      delta < 0: sin = u[k] + delta (u[k] - u[kl]).  Across the seam under WRAP the grid step on the
+ *      other side of k is used: k = K-1 with delta >= 0: u[k] - u[kl]; k = 0 with delta < 0:
+ *      u[kr] - u[k].  The result is not folded back into [-1, 1].
+ *   6. A non-finite s or u makes that row's outputs unspecified; it touches nothing else and nothing
+ *      out of bounds.
+ *   Measured errors of the sub-grid direction and the measured times: DESIGN.md 4.14,
+ *   profiles/doa_bench.json.
+ *   Parameters: n_ang = K in 1..256; r_lo, r_hi as fmcw_cfar_params; max_pk in 1..8; flags a subset
+ *     of FMCW_DOA_EDGES, FMCW_DOA_WRAP, FMCW_DOA_INV (EDGES with WRAP, or an unknown bit, is
+ *     FMCW_E_ARG; WRAP needs n_ang >= 3); min_abs finite and >= 0; min_rel in [0, 1]; min_prom finite
+ *     and >= 0.
+ * ------------------------------------------------------------------------- */
+enum { FMCW_DOA_EDGES = 1, FMCW_DOA_WRAP = 2, FMCW_DOA_INV = 4 };
+typedef struct fmcw_doa_params {
+  int32_t n_ang;           /* K, look directions, 1..256 */
+  int32_t r_lo, r_hi;      /* range gate, 1-based inclusive; 0, 0: all rows */
+  int32_t max_pk;          /* written peaks per row, 1..8 */
+  int32_t flags;           /* FMCW_DOA_* */
+  float   min_abs;         /* keep s[k] >= min_abs; >= 0 */
+  float   min_rel;         /* keep s[k] >= min_rel * the row's maximum; 0..1 */
+  float   min_prom;        /* keep s[k] >= min_prom * base; >= 0, 0: off */
+} fmcw_doa_params;
+
+/* Host only, no context: FMCW_E_ARG (with a message) for any violation of the constraints. */
+int fmcw_doa_check(const fmcw_doa_params* q, int32_t nr);
+
+/* Device pointers (every one given 16-byte aligned; *q is read on the host), asynchronous on
+ * `stream`; needs no fmcw_set_taps.  Acts on the context's first device.  d_spec [F][nr][n_ang];
+ * d_sin_theta [n_ang]; d_count, d_idx, d_pow, d_sin, d_base as above, any of them NULL (not written)
+ * but not all.  F = 0 is a no-op.  FMCW_E_ARG is returned before any launch: the outputs are then
+ * untouched. */
+int fmcw_doa_device(fmcw_ctx* ctx, const fmcw_doa_params* q, const float* d_spec, int64_t F, int32_t nr,
+                    const float* d_sin_theta, int32_t* d_count, int32_t* d_idx, float* d_pow, float* d_sin,
+                    float* d_base, void* stream);
+
+/* Host pointers (no alignment asked for): staged, frames sharded over the context's devices and
+ * chunked as fmcw_music is (fmcw_set_chunk_frames, when set, gives the frames of a chunk;
+ * bit-identical shards and chunks); returns when the outputs are on the host.  Any output may be
+ * NULL, not all. */
+int fmcw_doa(fmcw_ctx* ctx, const fmcw_doa_params* q, const float* spec, int64_t F, int32_t nr, const float* sin_theta,
+             int32_t* count, int32_t* idx, float* pow, float* sin, float* base);
 
 /* ---------------------------------------------------------------------------
  * spectrogram.png, replacing radar_processing.m:331-348:

@@ -113,6 +113,16 @@
  *                                        eval A x (Nr*F) single (ascending), evec (2*A*A) x (Nr*F) single
  *                                        (reshape(evec, 2, A, A, Nr, F): re and im; component; eigenvector), music_max
  *                                        a double
+ *   [idx, count, pow, sn, base] = fmcw_mex('doa', Q, spec, nr, sin_theta)
+ *                                                                 -> fmcw_doa: directions of arrival (beyond the
+ *                                        reference), the peaks of an angular spectrum per range row; Q: a struct with
+ *                                        the fields r_lo, r_hi, max_pk, flags (FMCW_DOA_EDGES = 1, FMCW_DOA_WRAP = 2,
+ *                                        FMCW_DOA_INV = 4), min_abs, min_rel, min_prom; spec: real single K x (Nr*F),
+ *                                        what 'ra' or 'music' returns, K in 1..256; nr: the rows of one frame;
+ *                                        sin_theta: the K grid values the weight table was formed on; idx is
+ *                                        max_pk x (Nr*F) int32, 0-based grid points by descending power, -1 in unused
+ *                                        slots; count 1 x (Nr*F) int32 (it may exceed max_pk); pow, sn (the sub-grid
+ *                                        sin(theta)) and base max_pk x (Nr*F) single
  *   fmcw_mex('close')                                            -> fmcw_ctx_destroy
  *
  * P is a struct with the fields of fmcw_params (nts, pn, nr, nd, max_targets,
@@ -760,6 +770,48 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (nlhs > 2) plhs[2] = eval;
     if (nlhs > 3) plhs[3] = evec;
     if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)mx);
+    return;
+  }
+  if (!strcmp(cmd, "doa")) {                /* [idx, count, pow, sn, base] = fmcw_mex('doa', Q, spec, nr, sin_theta) */
+    if (nrhs != 5) mexErrMsgIdAndTxt("fmcw:arg", "doa: Q, spec, nr, sin_theta");
+    const mxArray* s = prhs[1];
+    const mxArray* spec = prhs[2];
+    const mxArray* st = prhs[4];
+    if (!mxIsStruct(s)) mexErrMsgIdAndTxt("fmcw:arg", "Q must be a struct");
+    if (!mxIsSingle(spec) || mxIsComplex(spec) || mxGetNumberOfDimensions(spec) != 2)
+      mexErrMsgIdAndTxt("fmcw:arg", "spec must be real single K x (Nr*F)");
+    const mwSize K = mxGetM(spec);
+    const int32_t nr = (int32_t)mxGetScalar(prhs[3]);
+    if (K < 1 || K > 256 || nr < 1 || mxGetN(spec) % (mwSize)nr)
+      mexErrMsgIdAndTxt("fmcw:arg", "spec must have K rows, K in 1..256, and a multiple of nr columns");
+    const int64_t F = (int64_t)(mxGetN(spec) / (mwSize)nr);
+    if (!mxIsDouble(st) || mxIsComplex(st) || mxGetNumberOfElements(st) != K)
+      mexErrMsgIdAndTxt("fmcw:arg", "sin_theta must be a real double array of K values");
+    fmcw_doa_params q;
+    memset(&q, 0, sizeof q);
+    q.n_ang = (int32_t)K;
+    q.r_lo = (int32_t)field(s, "r_lo");
+    q.r_hi = (int32_t)field(s, "r_hi");
+    q.max_pk = (int32_t)field(s, "max_pk");
+    q.flags = (int32_t)field(s, "flags");
+    q.min_abs = (float)field(s, "min_abs");
+    q.min_rel = (float)field(s, "min_rel");
+    q.min_prom = (float)field(s, "min_prom");
+    check(fmcw_doa_check(&q, nr));
+    float* u = (float*)mxCalloc(K, sizeof(float));                          /* freed with the MEX call's memory */
+    for (mwSize i = 0; i < K; ++i) u[i] = (float)mxGetDoubles(st)[i];
+    const mwSize rows = mxGetN(spec);
+    plhs[0] = mxCreateNumericMatrix((mwSize)q.max_pk, rows, mxINT32_CLASS, mxREAL);
+    mxArray* count = mxCreateNumericMatrix(1, rows, mxINT32_CLASS, mxREAL);
+    mxArray* pw = mxCreateNumericMatrix((mwSize)q.max_pk, rows, mxSINGLE_CLASS, mxREAL);
+    mxArray* sn = mxCreateNumericMatrix((mwSize)q.max_pk, rows, mxSINGLE_CLASS, mxREAL);
+    mxArray* base = mxCreateNumericMatrix((mwSize)q.max_pk, rows, mxSINGLE_CLASS, mxREAL);
+    check(fmcw_doa(g_ctx, &q, mxGetSingles(spec), F, nr, u, mxGetInt32s(count), mxGetInt32s(plhs[0]), mxGetSingles(pw),
+                   mxGetSingles(sn), mxGetSingles(base)));
+    if (nlhs > 1) plhs[1] = count;
+    if (nlhs > 2) plhs[2] = pw;
+    if (nlhs > 3) plhs[3] = sn;
+    if (nlhs > 4) plhs[4] = base;
     return;
   }
   mexErrMsgIdAndTxt("fmcw:arg", "unknown command '%s'", cmd);
